@@ -29,12 +29,21 @@ ordinary streams are kept).
 Every rank owns its own atlases (weak scaling); the transcode needs no data-path collective.  The all-gather that
 reassembles the array is timed separately and reported under "allgather" -- never folded into `value`.
 
+A plain run does only what the headline needs: set-up, the clock ramp and W warm-up steps, ONE window of exactly K timed steps,
+the outputs (--dump-outputs) and the result line.  Everything else -- the known-answer gate, round 5's pipeline, the context rows,
+the child rocprofv3 passes, the CPU baseline, the all-gather of N > 1 and the median of --repeats windows -- runs with --full.
+
 Prints ONE JSON line (rank 0): metric/value per the driver contract plus
   roofline      algorithmic bytes (32 B/block x 64 x 2^20 blocks per launch) / the launch's average duration measured with
-                HIP events around the timed launches, against the 8 TB/s HBM peak; rocprofv3's own average for the same
-                launch and its HBM traffic from this run's child rocprofv3 passes
-  cpu_baseline  the oracle (C restatement of the reference CPU path, kind "port") timed on this box's
+                HIP events around the timed launches, against the 8 TB/s HBM peak; with --full rocprofv3's own average for the
+                same launch and its HBM traffic from this run's child rocprofv3 passes
+  cpu_baseline  (--full) the oracle (C restatement of the reference CPU path, kind "port") timed on this box's
                 host cores on a bounded sample of the same atlas
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files, a fixed sample of blocks:
+  atlas4096  DIR/bc7_blocks.npy  [atlases of the step, 8192 blocks, 16 bytes] (--method pipeline: the one atlas of the last timed launch)
+  array512   DIR/bc7_blocks.npy  [1, 524288 blocks of this rank's range, 16 bytes]
+the sampled block numbers are DIR/block_index.npy (float64; the same in every run: np.random.default_rng(DUMP_SEED)).
 """
 import argparse
 import ctypes
@@ -53,6 +62,9 @@ N_BLOCKS = NBX * NBY
 BYTES_PER_BLOCK = 32  # 16 read + 16 written
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 ATLASES_PER_STEP = 64  # --method batch: one step = ONE launch over this many 4096x4096 atlases in separate allocations (at most BU_MULTI_RUNS = 96 runs per launch)
+METRIC_ATLAS4096 = "M 4x4 blocks/s UASTC->BC7 4096x4096"
+DUMP_SEED = 20240917  # --dump-outputs: the blocks sampled from every output of the last timed step
+DUMP_BLOCKS = 1 << 19  # ... at most this many blocks in all (x 16 bytes x 4 as float32 = 32 MiB)
 ETC1S_UNPINNED = "unpinned: the reference holds no ETC1S / BasisLZ vectors (tests/corpus_tests.rs:54-73 are #[ignore]d, the corpus absent); checked against the oracle's reading of the source"
 
 
@@ -388,6 +400,20 @@ def cpu_baseline(golden, idx, budget_s=12.0):
     }
 
 
+def dump_outputs(dirname, outs, n_blocks):
+    """--dump-outputs: the same seeded sample of blocks from each of `outs` (device tensors of n_blocks x 16 bytes, what the last timed step wrote)
+    -> DIR/bc7_blocks.npy, float32 [len(outs), sample, 16]; the sampled block numbers -> DIR/block_index.npy (float64)"""
+    import torch
+
+    per = min(n_blocks, max(1, DUMP_BLOCKS // len(outs)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_blocks, size=per, replace=False))
+    sel = torch.from_numpy(pick).to(outs[0].device)
+    got = torch.stack([o.view(n_blocks, 16)[sel] for o in outs]).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "bc7_blocks.npy"), got.astype(np.float32))
+    np.save(os.path.join(dirname, "block_index.npy"), pick.astype(np.float64))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: run the N ranks as a child torch.distributed.run (never re-exec: this
     process has not touched a GPU -- device_count() does not initialise one on this image -- and must not)."""
@@ -443,18 +469,25 @@ def main():
     ap.add_argument("--policy", choices=("shared", "exclusive"), default=None,
                     help="launch policy of the context (bu_context_set_launch_policy): shared = a launch keeps at most half of every CU so that launches "
                          "of different streams run side by side (default when --in-flight > 1), exclusive = a launch fills the chip by itself")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (lead launches, exactly K timed launches, tail) is run this many times back to back and the MEDIAN window is "
-                         "reported; every window is listed in config.timed_region.windows_us_per_step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+                         "reported; every window is listed in config.timed_region.windows_us_per_step (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline, as every run did up to round 6: the known-answer gate, round 5's pipeline next to the batch "
+                         "headline, the context rows, the child rocprofv3 passes, the CPU baseline, the all-gather of N > 1, five timed windows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a fixed, seeded sample of what the last timed step computed to DIR/bc7_blocks.npy (float32; the block numbers: DIR/block_index.npy, float64), rank 0")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the verified, timed headline launches (no context rows, no CPU leg): the command profiled with rocprofv3, "
+                    help="with --full: only the verified, timed headline launches (no context rows, no CPU leg): the command profiled with rocprofv3, "
                          "so that its per-kernel average is the average of exactly the timed launches")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two child rocprofv3 counter passes that measure roofline.traffic (N = 1 only; ~1 min); the committed passes "
+                    help="with --full: do not run the two child rocprofv3 counter passes that measure roofline.traffic (N = 1 only; ~1 min); the committed passes "
                          "under profiles/ are quoted instead")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # Launches on different streams overlap only when the streams sit on different HARDWARE queues, and the HIP runtime hands a process
     # GPU_MAX_HW_QUEUES (default 4) of them per priority level, two of which torch's NULL stream and the context's internal stream already
@@ -474,10 +507,10 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)  # does not return
     # roofline.traffic, measured: the counter passes are child processes, started before this process touches the GPU
-    live = (None, "not requested", None)
+    live = (None, "not requested" if args.full else "not requested: --full measures it", None)
     import torch  # (pays the cold first import of a fresh box here, before the children are clocked; importing initialises no GPU)
     assert not torch.cuda.is_initialized()
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config == "atlas4096" and not args.headline_only and not args.no_live_traffic
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.config == "atlas4096" and not args.headline_only and not args.no_live_traffic
             and os.environ.get("BENCH_FORCE_DIST") != "1"):
         live = live_traffic(args.in_flight, args.policy, batch=args.method == "batch")
 
@@ -806,17 +839,18 @@ def batch_headline(env, line, in_ptrs, out_ptrs, nbuf, outs, idxs, status):
         n_step[0] += 1
         check(env, lib.bu_uastc_transcode_batch_device(ctx.handle, env._lib.BC7, A, a_[0], a_[1], a_[2], NBX, None, stp, stream_ptr or sp), "bu_uastc_transcode_batch_device")
 
-    # correctness gate through this very path: every atlas of the step against the known answers
-    for k in range(A):
-        outs[k].zero_()
     ctx.status_word_reset(status)
-    torch.cuda.synchronize()
-    step()
-    torch.cuda.synchronize()
-    ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
-    for k in range(A):
-        if not torch.equal(outs[k], env.g_bc7[idxs[k]]):
-            raise SystemExit("bench: BC7 output of atlas %d (batch step) differs from the known-answer vectors" % k)
+    if args.full:
+        # correctness gate through this very path: every atlas of the step against the known answers
+        for k in range(A):
+            outs[k].zero_()
+        torch.cuda.synchronize()
+        step()
+        torch.cuda.synchronize()
+        ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
+        for k in range(A):
+            if not torch.equal(outs[k], env.g_bc7[idxs[k]]):
+                raise SystemExit("bench: BC7 output of atlas %d (batch step) differs from the known-answer vectors" % k)
     t_pre, prewarm_steps = time.perf_counter(), 0
     while args.prewarm_ms > 0 and (time.perf_counter() - t_pre) * 1e3 < 4 * args.prewarm_ms:  # (launches of this size take ~100 ms to settle the clocks, as config 5's)
         for _ in range(8):
@@ -858,16 +892,20 @@ def batch_headline(env, line, in_ptrs, out_ptrs, nbuf, outs, idxs, status):
     m_ = sorted(range(R_), key=lambda i: dts[i])[R_ // 2]
     dt, ev = dts[m_], evs[m_]
     ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
+    if args.dump_outputs and rank == 0:
+        last = (n_step[0] - 1) % len(sets)
+        dump_outputs(args.dump_outputs, [outs[last * A + j] for j in range(A)], N_BLOCKS)
     K = args.steps
     step_s = ev / K
     achieved = BYTES_PER_BLOCK * A * N_BLOCKS / step_s / 1e9
-    old_roof = line["roofline"]
-    line["one_launch_per_atlas_in_flight"] = {
-        "value": line["value"], "unit": line["unit"], "us_per_atlas": round(line["ms_per_step"] * 1e3, 3), "launches_in_flight": line["config"].get("launches_in_flight"),
-        "launch_policy": line["config"].get("launch_policy"), "workload": line["config"]["workload"], "timed_region": line["config"].pop("timed_region", None),
-        "roofline": {k_: v_ for k_, v_ in old_roof.items() if k_ not in ("one_launch_of_32_contiguous_atlases",)},
-        "note": "rounds 5's headline, measured in this run by its own method: one launch per atlas, step i on context stream i % in_flight, K timed launches between per-stream events "
-                "(window = last lead launch complete -> last timed launch complete); a pipeline's throughput is a PERIOD, which rocprofv3 does not report"}
+    old_roof = line.get("roofline") or {}
+    if args.full:  # (the line holds the pipeline's figures)
+        line["one_launch_per_atlas_in_flight"] = {
+            "value": line["value"], "unit": line["unit"], "us_per_atlas": round(line["ms_per_step"] * 1e3, 3), "launches_in_flight": line["config"].get("launches_in_flight"),
+            "launch_policy": line["config"].get("launch_policy"), "workload": line["config"]["workload"], "timed_region": line["config"].pop("timed_region", None),
+            "roofline": {k_: v_ for k_, v_ in old_roof.items() if k_ not in ("one_launch_of_32_contiguous_atlases",)},
+            "note": "rounds 5's headline, measured in this run by its own method: one launch per atlas, step i on context stream i % in_flight, K timed launches between per-stream events "
+                    "(window = last lead launch complete -> last timed launch complete); a pipeline's throughput is a PERIOD, which rocprofv3 does not report"}
     live = env.live_traffic
     tr = live[2] if len(live) > 2 and isinstance(live[2], dict) else None
     rp = (tr or {}).get("batch")
@@ -903,7 +941,7 @@ def batch_headline(env, line, in_ptrs, out_ptrs, nbuf, outs, idxs, status):
         "note": "achieved = algorithmic bytes per launch (32 B x 2^20 blocks x %d atlases) / the launch's average duration = HIP events around the K timed launches / K; "
                 "rocprofv3_this_run: the same launch's per-kernel duration from a child `rocprofv3 --kernel-trace` pass of this run (240 launches, the last half counted); "
                 "traffic: child --pmc FETCH_SIZE / WRITE_SIZE passes over the same launch, (2 x FETCH + WRITE) KiB (the gfx950 read correction).  The three clocks agree because "
-                "the step is ONE kernel; `one_launch_per_atlas_in_flight` has round 5's pipeline, measured in this run too" % A}
+                "the step is ONE kernel; `one_launch_per_atlas_in_flight` has round 5's pipeline, measured in a --full run too" % A}
     return line
 
 
@@ -977,15 +1015,16 @@ def run_array512(env):
     def expect(s):
         return env.g_bc7[slice_idx(s)]
 
-    # correctness gate: this rank's whole shard of rotation slot 0
-    run(1)
-    torch.cuda.synchronize()
-    ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
-    mine = fulls[0].tensor()[rank * shard_bytes: rank * shard_bytes + nb * 16].view(-1, bps, 16)
-    for k, s in enumerate(range(lo, hi)):
-        if not torch.equal(mine[k], expect(s)):
-            raise SystemExit("bench: BC7 output of slice %d differs from the known-answer vectors" % s)
-    rot[0] = 1 % nrot
+    if args.full:
+        # correctness gate: this rank's whole shard of rotation slot 0
+        run(1)
+        torch.cuda.synchronize()
+        ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
+        mine = fulls[0].tensor()[rank * shard_bytes: rank * shard_bytes + nb * 16].view(-1, bps, 16)
+        for k, s in enumerate(range(lo, hi)):
+            if not torch.equal(mine[k], expect(s)):
+                raise SystemExit("bench: BC7 output of slice %d differs from the known-answer vectors" % s)
+        rot[0] = 1 % nrot
     prewarm_launches = 0
     t_pre = time.perf_counter()
     # clock ramp, untimed (see --prewarm-ms); the 1 GiB-per-launch kernel takes about four times as long to settle
@@ -1008,6 +1047,7 @@ def run_array512(env):
     #  after an idle moment the 2^23..2^25-block launches run 10-25 % slower for tens of milliseconds -- with 16 lead steps the one-rank run of this
     #  branch read 208-213 us per step where the same launches without torch.distributed read 175: profiles/r05_dist_branch_hw_queues.txt)
     lead = int(os.environ.get("BENCH_ARRAY_LEAD", "128"))
+    slot_last = (rot[0] + lead + args.steps - 1) % nrot  # the rotation slot of the last timed step
     ev_ms, host_ms = window(lead, args.steps)
     torch.cuda.synchronize()
     # the streams have to be in step for the window to hold `steps` completions of every stream (run_atlas4096 has the story): start events more than
@@ -1022,9 +1062,12 @@ def run_array512(env):
     if out_of_step:
         ctx.set_launch_policy("auto")
         window(0, 2, pieces=1)
+        slot_last = (rot[0] + 4 + args.steps - 1) % nrot
         ev_ms, host_ms = window(4, args.steps, pieces=1)
         torch.cuda.synchronize()
         P_timed = 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [fulls[slot_last].tensor()[rank * shard_bytes: rank * shard_bytes + nb * 16]], nb)
     dt = max(host_ms, ev_ms) / 1e3
     if env.use_dist:
         dist.barrier()
@@ -1071,7 +1114,7 @@ def run_array512(env):
                      "bytes_per_launch": BYTES_PER_BLOCK * nb, "note": "per GPU, on its shard"},
     }
     gather = None
-    if env.use_dist:
+    if env.use_dist and args.full:
         # shard of rotation slot 0 is verified above; re-run it so that slot 0 holds this rank's result, then gather slot 0
         rot[0] = 0
         run(1)
@@ -1123,6 +1166,11 @@ def run_atlas4096(env):
     PtrArr = ctypes.c_void_p * nbuf
     in_ptrs = PtrArr(*[t.data_ptr() for t in ins])
     out_ptrs = PtrArr(*[t.data_ptr() for t in outs])
+    if args.method == "batch" and not args.full:
+        # a plain run: the headline's batch steps and nothing else (round 5's pipeline, the context rows and the CPU leg run with --full)
+        line = {"metric": METRIC_ATLAS4096, "value": None, "unit": "Mblocks/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "config": {}}
+        return batch_headline(env, line, in_ptrs, out_ptrs, nbuf, outs, idxs, status)
     # Rotation position carried across EVERY call: a timed launch never re-touches what the warm-up (or any earlier
     # row) just touched, whatever --warmup is.
     rot = [0]
@@ -1219,13 +1267,14 @@ def run_atlas4096(env):
     effective_streams, stream_mode = ctx.query_in_flight(args.in_flight) if args.in_flight > 1 else (1, "pool")  # (what the library found when it created its streams)
     ctx.status_word_reset(status)
     torch.cuda.synchronize()  # (the context's streams do not wait for torch's)
-    run_window(0, nbuf)       # one launch per atlas, round-robin over the streams
-    rot[0] = 0
-    torch.cuda.synchronize()
-    ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
-    for k in range(nbuf):
-        if not torch.equal(outs[k], g_bc7[idxs[k]]):
-            raise SystemExit("bench: BC7 output of atlas %d differs from the known-answer vectors" % k)
+    if args.full:
+        run_window(0, nbuf)       # one launch per atlas, round-robin over the streams
+        rot[0] = 0
+        torch.cuda.synchronize()
+        ctx.status_word_check(int(status.item()) & 0xFFFFFFFFFFFFFFFF)
+        for k in range(nbuf):
+            if not torch.equal(outs[k], g_bc7[idxs[k]]):
+                raise SystemExit("bench: BC7 output of atlas %d differs from the known-answer vectors" % k)
 
     # ---- clock ramp (untimed, see --prewarm-ms), W warm-up steps, then EXACTLY K timed steps between barrier + synchronize ----
     prewarm_launches = 0
@@ -1257,9 +1306,12 @@ def run_atlas4096(env):
     lead = max(2048, 2 * args.steps)
     wins = []
     for r_ in range(max(1, args.repeats)):
+        k_last = (rot[0] + lead + args.steps - 1) % nbuf  # the atlas of the window's last timed launch
         ev_ms_, host_ms_, late_ = run_window(lead, args.steps)
         wins.append((max(host_ms_, ev_ms_), ev_ms_, host_ms_, late_, window_streams()))
     torch.cuda.synchronize()
+    if args.dump_outputs and args.method == "pipeline" and rank == 0:
+        dump_outputs(args.dump_outputs, [outs[k_last]], N_BLOCKS)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1301,16 +1353,19 @@ def run_atlas4096(env):
     # the strict bracket: the same K steps with NOTHING behind them, from the first instruction of the first timed launch to the last instruction
     # of the last one (the pipeline's fill is credited to nobody and its drain -- the last launches running with fewer and fewer partners -- is inside)
     stricts = []
-    for _ in range(max(1, args.repeats)):  # (median of the same number of passes as the headline: one 0.12 ms window is at the mercy of a single stall)
+    for _ in range(max(1, args.repeats) if args.full else 0):  # (median of the same number of passes as the headline: one 0.12 ms window is at the mercy of a single stall)
         run_window(lead, args.steps, tail=0)
         stricts.append((fill_drain[0] / 1e3 / args.steps, window_streams()))
-    strict_s, strict_streams = sorted(stricts, key=lambda x: x[0])[len(stricts) // 2]
+    strict_s, strict_streams = sorted(stricts, key=lambda x: x[0])[len(stricts) // 2] if stricts else (None, None)
     # ---- the round 1-4 headline, kept as a row: ONE launch at a time (exclusive policy, one stream), same window method ----
-    policy_now[0] = False
-    ctx.set_launch_policy(False)
-    run_window(0, 256, in_flight=1)
-    one_ev, one_host, _ = run_window(lead, args.steps, in_flight=1)
-    one_s = max(one_ev, one_host) / 1e3 / args.steps
+    # (without --full only when it becomes the headline: streams out of step)
+    one_s = None
+    if args.full or out_of_step:
+        policy_now[0] = False
+        ctx.set_launch_policy(False)
+        run_window(0, 256, in_flight=1)
+        one_ev, one_host, _ = run_window(lead, args.steps, in_flight=1)
+        one_s = max(one_ev, one_host) / 1e3 / args.steps
     if out_of_step:
         o_ = torch.tensor([one_s], dtype=torch.float64, device=dev)
         if use_dist:
@@ -1319,24 +1374,26 @@ def run_atlas4096(env):
         value = total_blocks / dt_max / 1e6
         period_s = ev_max / args.steps
         achieved = BYTES_PER_BLOCK * N_BLOCKS / period_s / 1e9
-    # per-launch distribution: one event between every two launches of another K steps
-    each = (ctypes.c_float * args.steps)()
-    st = lib.bu_time_uastc_launches_each(ctx.handle, _lib.BC7, in_ptrs, out_ptrs, nbuf, rot[0] % nbuf, N_BLOCKS, NBX, args.steps,
-                                         ctypes.c_void_p(status.data_ptr()), sp, each)
-    rot[0] += args.steps
-    per_launch = None
-    if st == 0:
-        v = np.sort(np.array(list(each), dtype=np.float64))
-        per_launch = {"median_us": round(float(np.median(v)), 3), "min_us": round(float(v[0]), 3), "p90_us": round(float(v[int(0.9 * (len(v) - 1))]), 3),
-                      "max_us": round(float(v[-1]), 3),
-                      "note": "event-to-event time of each launch in a separate pass of K steps, one launch at a time (the event packets between launches are included)"}
-    one_row = {"us_per_launch": round(one_s * 1e6, 3), "mblocks_s": round(N_BLOCKS / one_s / 1e6, 1), "gb_s": round(BYTES_PER_BLOCK * N_BLOCKS / one_s / 1e9, 1),
-               "frac_of_hbm_peak": round(BYTES_PER_BLOCK * N_BLOCKS / one_s / 1e9 / HBM_PEAK_GBS, 4), "launch_policy": "exclusive", "per_launch": per_launch,
-               "note": "the headline of rounds 1-4: K launches back to back on ONE stream, exclusive launch policy (a launch fills the chip by itself); "
-                       "consecutive launches of one stream do not overlap, so this is also one launch's own duration"}
+    one_row = None
+    if args.full:
+        # per-launch distribution: one event between every two launches of another K steps
+        each = (ctypes.c_float * args.steps)()
+        st = lib.bu_time_uastc_launches_each(ctx.handle, _lib.BC7, in_ptrs, out_ptrs, nbuf, rot[0] % nbuf, N_BLOCKS, NBX, args.steps,
+                                             ctypes.c_void_p(status.data_ptr()), sp, each)
+        rot[0] += args.steps
+        per_launch = None
+        if st == 0:
+            v = np.sort(np.array(list(each), dtype=np.float64))
+            per_launch = {"median_us": round(float(np.median(v)), 3), "min_us": round(float(v[0]), 3), "p90_us": round(float(v[int(0.9 * (len(v) - 1))]), 3),
+                          "max_us": round(float(v[-1]), 3),
+                          "note": "event-to-event time of each launch in a separate pass of K steps, one launch at a time (the event packets between launches are included)"}
+        one_row = {"us_per_launch": round(one_s * 1e6, 3), "mblocks_s": round(N_BLOCKS / one_s / 1e6, 1), "gb_s": round(BYTES_PER_BLOCK * N_BLOCKS / one_s / 1e9, 1),
+                   "frac_of_hbm_peak": round(BYTES_PER_BLOCK * N_BLOCKS / one_s / 1e9 / HBM_PEAK_GBS, 4), "launch_policy": "exclusive", "per_launch": per_launch,
+                   "note": "the headline of rounds 1-4: K launches back to back on ONE stream, exclusive launch policy (a launch fills the chip by itself); "
+                           "consecutive launches of one stream do not overlap, so this is also one launch's own duration"}
 
     extra = {}
-    if rank == 0 and not args.headline_only:
+    if rank == 0 and args.full and not args.headline_only:
         # context rows (not the headline): copy ceiling of the same shape, hot-cache and coherent atlases, RGBA32
         ms = ctypes.c_float(0)
         lib.bu_time_copy_launches(ctx.handle, in_ptrs, out_ptrs, nbuf, rot[0] % nbuf, N_BLOCKS, 32, sp, ctypes.byref(ms))
@@ -2070,7 +2127,7 @@ def run_atlas4096(env):
 
 
     line = {
-        "metric": "M 4x4 blocks/s UASTC->BC7 4096x4096",
+        "metric": METRIC_ATLAS4096,
         "value": round(value, 1),
         "unit": "Mblocks/s",
         "n_gpus": world,
@@ -2113,8 +2170,8 @@ def run_atlas4096(env):
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "traffic_source": None,
                      "kernel": "bu_uastc_sorted_kernel<BC7> (%s-policy shape)" % args.policy,
                      "launches_in_flight": args.in_flight, "period_ns": round(period_s * 1e9, 1), "us_per_launch": round(period_s * 1e6, 3),
-                     "strict_bracket_ns_per_step": round(strict_s * 1e9, 1),
-                     "frac_by_strict_bracket": round(BYTES_PER_BLOCK * N_BLOCKS / strict_s / 1e9 / HBM_PEAK_GBS, 4),
+                     "strict_bracket_ns_per_step": round(strict_s * 1e9, 1) if strict_s else None,
+                     "frac_by_strict_bracket": round(BYTES_PER_BLOCK * N_BLOCKS / strict_s / 1e9 / HBM_PEAK_GBS, 4) if strict_s else None,
                      "bytes_per_launch": BYTES_PER_BLOCK * N_BLOCKS,
                      "note": "achieved = algorithmic bytes per launch / launch-to-launch PERIOD of the K timed launches = (HIP event behind the last timed launch - HIP "
                              "event behind the last lead launch, latest over the streams) / K: K launches complete in that window and the pipeline is full at both ends.  "
@@ -2180,7 +2237,8 @@ def run_atlas4096(env):
             rate = tr[2] / period_s / 1e9
             extra["valu_issue"] = {"wave_instructions_per_launch": int(tr[2]), "achieved_g_per_s": round(rate, 1), "peak_g_per_s": round(peak, 1),
                                    "frac": round(rate / peak, 3), "source": tr[1] + " (SQ_INSTS_VALU of the committed counter pass -- read from that file, NOT measured in this run)"}
-    extra["one_launch_at_a_time"] = one_row
+    if one_row:
+        extra["one_launch_at_a_time"] = one_row
     a1_ = extra.get("array512_one_launch")
     a32_ = (env.live_traffic[2] or {}).get("array32") if len(env.live_traffic) > 2 and isinstance(env.live_traffic[2], dict) else None
     if a1_ and a1_.get("verified"):
@@ -2198,7 +2256,7 @@ def run_atlas4096(env):
                     "workgroups draw their tiles by ticket (round 6)"}
     line["extra"] = extra
     allgather = None
-    if use_dist:
+    if use_dist and args.full:
         # reassembly of the texture array: every rank's 16 MiB BC7 result at rank*16 MiB of a world*16 MiB buffer on every rank
         shard_bytes = N_BLOCKS * 16
         full = RawDeviceBuffer(env, world * shard_bytes)
@@ -2227,7 +2285,7 @@ def run_atlas4096(env):
             raise
         except Exception as e:  # the pipeline's line stands, and says why
             line["config"]["method"] = "pipeline (the batch step failed: %r)" % (e,)
-    if world == 1 and rank == 0 and not args.no_cpu and not args.headline_only:
+    if world == 1 and rank == 0 and args.full and not args.no_cpu and not args.headline_only:
         line["cpu_baseline"] = cpu_baseline(golden, idx0)
     return line
 

@@ -474,7 +474,7 @@ def test_bench_array512_mode_on_one_gpu():
     import subprocess
 
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "array512", "--steps", "3", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "array512", "--steps", "3", "--warmup", "1"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

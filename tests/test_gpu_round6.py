@@ -571,7 +571,7 @@ def test_bench_default_method_is_one_launch_per_64_atlases():
         env = dict(os.environ)
         if force_dist:
             env["BENCH_FORCE_DIST"] = "1"
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--headline-only", "--no-cpu", "--no-live-traffic", "--steps", "6", "--warmup", "2"], env=env,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--headline-only", "--no-cpu", "--no-live-traffic", "--steps", "6", "--warmup", "2"], env=env,
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -583,3 +583,22 @@ def test_bench_default_method_is_one_launch_per_64_atlases():
         assert roof["atlases_per_launch"] == 64 and 0.55 < roof["frac"] < 0.9 and roof["bytes_per_launch"] == 64 * 32 << 20
         pipe = line["one_launch_per_atlas_in_flight"]
         assert 4.8 < pipe["us_per_atlas"] < 9.0 and pipe["roofline"]["bound"] == "hbm"
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path, golden):
+    """bench.py without --full: one window of exactly K batch steps, none of the --full rows, and --dump-outputs writes a seeded sample of the last
+    step's 64 BC7 atlases as float32 (at most 64 MB) that equals the known answers of atlas 0 (rank 0's first atlas: synth.gold_indices)"""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["config"]["method"] == "batch" and line["config"]["timed_region"]["repeats"] == 1
+    assert line["metric"] == "M 4x4 blocks/s UASTC->BC7 4096x4096" and line["unit"] == "Mblocks/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert abs(line["value"] - 64 * (1 << 20) / (line["ms_per_step"] * 1e-3) / 1e6) < 0.01 * line["value"]
+    assert "one_launch_per_atlas_in_flight" not in line and "cpu_baseline" not in line and "extra" not in line
+    blocks, pick = np.load(out / "bc7_blocks.npy"), np.load(out / "block_index.npy")
+    assert blocks.dtype == np.float32 and pick.dtype == np.float64 and blocks.shape == (64, pick.size, 16)
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    want = golden["bc7"][synth.gold_indices(1 << 20)[pick.astype(np.int64)]]
+    assert (blocks[0] == want).all()
