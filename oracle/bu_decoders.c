@@ -11,6 +11,9 @@
  *         the UASTC colours (bounded per-channel error) -- catches wrong partitions, swapped endpoints, un-inverted
  *         weights, misplaced p-bits.
  *   EAC   the ETC2 alpha half: decoded alpha must stay close to the UASTC alpha.
+ *   ETC1  the colour block of ETC1 and of ETC2 RGB(A) (bytes 8..16): individual / differential modes, both flip
+ *         orientations, the ETC2 T / H / planar modes detected (differential blocks whose base colour leaves 0..31);
+ *         the decoded fields are returned with the texels so that a test can rebuild every selector (tests/etc_model.py).
  *
  * Everything a conformant decoder derives from the bitstream is derived here (block mode, weight range, the colour
  * endpoint range from the bits left over, the partition from the hash function / the BPTC tables); nothing is taken
@@ -557,6 +560,69 @@ void bu_dec_eac_alpha(const uint8_t b[8], uint8_t out[16])
         }
 }
 
+/* ================================================================================================ ETC1 */
+/* ETC1 / ETC2 RGB colour block (8 bytes).  The 64-bit block is read big-endian: bytes 0..2 base colours, byte 3 = table
+ * codeword 1 (bits 7..5), table codeword 2 (bits 4..2), diff bit (1), flip bit (0); bytes 4..7 = the 32-bit pixel index word,
+ * most significant bits of the 16 texels in its upper half, least significant in its lower half, texel j = 4 * x + y (the
+ * texels run down the columns) at bit j of either half.
+ *   individual   (diff 0): two 4-bit base colours, R1 | R2 << 4 per byte, each extended by replication (x * 17).
+ *   differential (diff 1): a 5-bit base colour and a 3-bit two's-complement delta per byte; the second colour is their sum,
+ *                which must stay in 0..31 for ETC1.  ETC2 uses the overflow: R out of range = T mode, else G = H mode, else
+ *                B = planar mode.  5-bit values are extended as (x << 3) | (x >> 2).
+ *   flip 0: sub-block 1 = columns 0-1, sub-block 2 = columns 2-3;  flip 1: sub-block 1 = rows 0-1, sub-block 2 = rows 2-3.
+ *   pixel index (msb, lsb): 0 0 -> +a, 0 1 -> +b, 1 0 -> -a, 1 1 -> -b, {a, b} the row of the intensity table below.
+ * ETC2 T / H / planar blocks are detected, not decoded (their texels are returned as zeros). */
+static const int ETC1_INTEN[8][2] = {{2, 8}, {5, 17}, {9, 29}, {13, 42}, {18, 60}, {24, 80}, {33, 106}, {47, 183}};
+
+enum { ETC_INDIVIDUAL = 0, ETC_DIFFERENTIAL = 1, ETC_T = 2, ETC_H = 3, ETC_PLANAR = 4 };
+
+/* fields[32]: base colour 1 RGB (4 or 5 bits), base colour 2 RGB, codeword 1, codeword 2, diff, flip, ETC2 mode, 0, then the
+ * selector of each texel in ROW-major order as an index 0..3 into the table row in increasing order {-b, -a, +a, +b}, 4 zeros */
+int bu_dec_etc1(const uint8_t b[8], uint8_t out[64], uint8_t fields[32])
+{
+    memset(out, 0, 64);
+    memset(fields, 0, 32);
+    const int diff = (b[3] >> 1) & 1, flip = b[3] & 1;
+    const int cw[2] = {b[3] >> 5, (b[3] >> 2) & 7};
+    int base[2][3], mode = diff ? ETC_DIFFERENTIAL : ETC_INDIVIDUAL;
+    for (int c = 0; c < 3; c++) {
+        if (!diff) {
+            base[0][c] = b[c] >> 4;
+            base[1][c] = b[c] & 15;
+        } else {
+            const int d = (b[c] & 7) >= 4 ? (b[c] & 7) - 8 : (b[c] & 7);
+            base[0][c] = b[c] >> 3;
+            base[1][c] = base[0][c] + d;
+            if ((base[1][c] < 0 || base[1][c] > 31) && mode == ETC_DIFFERENTIAL) mode = c == 0 ? ETC_T : c == 1 ? ETC_H : ETC_PLANAR;
+        }
+    }
+    fields[6] = (uint8_t)cw[0];
+    fields[7] = (uint8_t)cw[1];
+    fields[8] = (uint8_t)diff;
+    fields[9] = (uint8_t)flip;
+    fields[10] = (uint8_t)mode;
+    if (mode > ETC_DIFFERENTIAL) return mode;
+    for (int s = 0; s < 2; s++)
+        for (int c = 0; c < 3; c++) fields[3 * s + c] = (uint8_t)base[s][c];
+    const uint32_t idx = (uint32_t)b[4] << 24 | (uint32_t)b[5] << 16 | (uint32_t)b[6] << 8 | b[7];
+    static const int TABLE_INDEX[4] = {2, 3, 1, 0}; /* pixel index value -> position in {-b, -a, +a, +b} */
+    for (int y = 0; y < 4; y++)
+        for (int x = 0; x < 4; x++) {
+            const int j = 4 * x + y, s = flip ? y >= 2 : x >= 2;
+            const int msb = (idx >> (16 + j)) & 1, lsb = (idx >> j) & 1;
+            const int a = ETC1_INTEN[cw[s]][0], bb = ETC1_INTEN[cw[s]][1];
+            const int mod = lsb ? (msb ? -bb : bb) : (msb ? -a : a);
+            fields[12 + 4 * y + x] = (uint8_t)TABLE_INDEX[2 * msb + lsb];
+            for (int c = 0; c < 3; c++) {
+                const int e = diff ? (base[s][c] << 3) | (base[s][c] >> 2) : base[s][c] * 17;
+                const int v = e + mod;
+                out[4 * (4 * y + x) + c] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+            }
+            out[4 * (4 * y + x) + 3] = 255;
+        }
+    return mode;
+}
+
 /* ---- batch wrappers for the ctypes tests ---- */
 void bu_dec_astc_batch(const uint8_t* in, size_t n, uint8_t* out, uint8_t* st)
 {
@@ -570,6 +636,15 @@ void bu_dec_eac_batch(const uint8_t* in, size_t stride, size_t n, uint8_t* out)
 {
     for (size_t i = 0; i < n; i++) bu_dec_eac_alpha(in + stride * i, out + 16 * i);
 }
+
+/* stride 8: ETC1 blocks; stride 16 with in + 8: the colour half of ETC2 RGBA blocks */
+void bu_dec_etc1_batch(const uint8_t* in, size_t stride, size_t n, uint8_t* out, uint8_t* fields)
+{
+    for (size_t i = 0; i < n; i++) bu_dec_etc1(in + stride * i, out + 64 * i, fields + 32 * i);
+}
+
+/* the specification's ETC1 intensity table {a, b} per codeword, exported for the tests' candidate colours */
+const int16_t ETC1_INTEN_EXPORT[16] = {2, 8, 5, 17, 9, 29, 13, 42, 18, 60, 24, 80, 33, 106, 47, 183};
 
 /* the specification's EAC modifier table, exported so that a test can rebuild a block's candidate values */
 const int8_t EAC_MOD_EXPORT[128] = {-3, -6, -9, -15, 2, 5, 8, 14, -3, -7, -10, -13, 2, 6, 9, 12, -2, -5, -8, -13, 1, 4, 7, 12, -2, -4, -6, -13, 1, 3, 5, 12,

@@ -140,7 +140,7 @@ class Oracle:
 
 
 class Decoders:
-    """ctypes view of oracle/libbu_decoders.so: independent ASTC / BC7 / EAC decoders (bu_decoders.c) -- test-only."""
+    """ctypes view of oracle/libbu_decoders.so: independent ASTC / BC7 / EAC / ETC1 decoders (bu_decoders.c) -- test-only."""
 
     def __init__(self):
         _make(os.path.join(ROOT, "oracle"), "libbu_decoders.so")
@@ -152,6 +152,8 @@ class Decoders:
         L.bu_dec_bc7_batch.restype = None
         L.bu_dec_eac_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p]
         L.bu_dec_eac_batch.restype = None
+        L.bu_dec_etc1_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_void_p]
+        L.bu_dec_etc1_batch.restype = None
         L.bu_dec_astc_partition_4x4.argtypes = [c.c_int] * 4
         L.bu_dec_bc7_subset.argtypes = [c.c_int] * 3
         L.bu_dec_bc7_anchor.argtypes = [c.c_int] * 3
@@ -176,3 +178,32 @@ class Decoders:
         out = np.zeros((b.shape[0], 16), dtype=np.uint8)
         self.lib.bu_dec_eac_batch(b.ctypes.data, 16, b.shape[0], out.ctypes.data)
         return out
+
+    # per-block fields of the ETC1 colour block, as bu_dec_etc1 fills them
+    ETC_FIELDS = np.dtype([("base", np.uint8, (2, 3)), ("cw", np.uint8, 2), ("diff", np.uint8), ("flip", np.uint8), ("mode", np.uint8),
+                           ("pad", np.uint8), ("sel", np.uint8, 16), ("pad2", np.uint8, 4)])
+    ETC_MODES = ("individual", "differential", "T", "H", "planar")
+
+    def _etc1(self, blocks8):
+        b = np.ascontiguousarray(blocks8, dtype=np.uint8).reshape(-1, 8)
+        out = np.zeros((b.shape[0], 64), dtype=np.uint8)
+        fields = np.zeros(b.shape[0], dtype=self.ETC_FIELDS)
+        self.lib.bu_dec_etc1_batch(b.ctypes.data, 8, b.shape[0], out.ctypes.data, fields.ctypes.data)
+        return out, fields
+
+    def etc1(self, blocks8):
+        """[n,8] ETC1 / ETC2 RGB colour blocks -> [n,64] RGBA8 row-major texels, alpha 255 (zeros for ETC2 T / H / planar blocks)"""
+        return self._etc1(blocks8)[0]
+
+    def etc1_fields(self, blocks8):
+        """[n,8] colour blocks -> structured [n] ETC_FIELDS: base (colour, channel) at 4 / 5 bits, cw, diff, flip, mode (index into
+        ETC_MODES), sel = the row-major texels' index 0..3 into the codeword's modifiers in increasing order"""
+        return self._etc1(blocks8)[1]
+
+    def etc1_both(self, blocks8):
+        return self._etc1(blocks8)
+
+    def etc1_intensity(self):
+        """the specification's intensity table as [8, 4] modifiers in increasing order {-b, -a, +a, +b}"""
+        ab = np.ctypeslib.as_array((ctypes.c_int16 * 16).in_dll(self.lib, "ETC1_INTEN_EXPORT")).reshape(8, 2).astype(int)
+        return np.stack([-ab[:, 1], -ab[:, 0], ab[:, 0], ab[:, 1]], axis=1)

@@ -128,9 +128,11 @@ def test_etc2_alpha_modes_with_a_zero_table_multiplier(ctx, golden, oracle):
 
 def test_etc1s_hip_outputs_decode_to_the_rgba_outputs(ctx, oracle):
     """The ETC1S path has no reference vectors; exact cross-check on the HIP outputs themselves: the ETC1
-    block bu_etc1s_transcode_etc1 emits, decoded with plain ETC1 rules (independent decoder), equals the texels
-    bu_etc1s_decode_rgba writes -- at 2^19 blocks, above the per-slice sizes the other tests use."""
+    block bu_etc1s_transcode_etc1 emits, decoded by the specification decoder (oracle/bu_decoders.c, independent of the
+    transcoder), equals the texels bu_etc1s_decode_rgba writes -- every one of 2^19 blocks, above the per-slice sizes the
+    other tests use."""
     from basisu_rs_amd import etc1s_selector_from_rows
+    from oracle.pyoracle import Decoders
 
     ep, rows = synth.etc1s_codebooks(4096, 8192, seed=3)
     sel = etc1s_selector_from_rows(rows)
@@ -143,14 +145,13 @@ def test_etc1s_hip_outputs_decode_to_the_rgba_outputs(ctx, oracle):
     # against the oracle at full size
     assert (etc1.reshape(-1) == oracle.etc1s_to_etc1(idx, ep, sel)).all()
     assert (rgba.reshape(-1) == oracle.etc1s_to_rgba(idx, None, nbx, nby, ep, sel)).all()
-    # the identity, on a sample (the per-block decoder call is a Python loop)
-    rng = np.random.default_rng(1)
-    for i in rng.choice(n, 4096, replace=False):
-        out = np.zeros(64, dtype=np.uint8)
-        blk = np.ascontiguousarray(etc1[i])
-        oracle.lib.bu_oracle_decode_etc1_block(blk.ctypes.data, out.ctypes.data)
-        assert (out == lin[i]).all(), i
-        assert etc1[i][3] & 3 == 3  # diff = 1, flip = 1 (basis_lz/mod.rs:177)
+    # the identity, on every block
+    texels, fields = Decoders().etc1_both(etc1)
+    bad = np.nonzero((texels != lin).any(axis=1))[0]
+    assert bad.size == 0, bad[:8]
+    assert (fields["diff"] == 1).all() and (fields["flip"] == 1).all()  # diff = 1, flip = 1 (basis_lz/mod.rs:177)
+    assert (fields["mode"] == 1).all()  # differential, never an ETC2 T / H / planar block
+    assert (etc1[:, 3] & 3 == 3).all()
 
 
 def test_rgba32_launch_splitting_above_2_pow_26_blocks(ctx, golden):
