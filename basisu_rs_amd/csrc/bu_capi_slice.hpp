@@ -208,146 +208,43 @@ bu_status bu_batch_runs(bu_context* ctx, bu_target target, size_t n_slices, cons
     return BU_OK;
 }
 
-// runs[0 .. n_runs) on ONE stream: one run is the plain launch; several runs at unrelated addresses are ONE launch per BU_MULTI_RUNS runs,
-// the run table in the kernel arguments (kernel layout MULTI).  policy: BU_POLICY_* of the plain launches, -1 = the context's.
+// runs[0 .. n_runs) on ONE stream, as bu_plan_runs plans them.  policy: BU_POLICY_* of the launches, -1 = the context's.
 bu_status bu_launch_runs(bu_context* ctx, bu_target target, const BuRun* runs, size_t n_runs, size_t blocks_per_row, uint64_t* d_status, hipStream_t s, int policy)
 {
     if (n_runs == 0) return BU_OK;
     if (n_runs == 1) return bu_launch_uastc(ctx, target, runs[0].in, runs[0].n, runs[0].out, blocks_per_row, runs[0].base, d_status, s, 0, policy);
-    // Launching the runs one by one is bound by the ~4 us of host time per launch whatever the number of streams (64 slices
-    // of 65 536 blocks: 290 us on one stream, 230-260 us on 2-8, profiles/r03_small_slices_streams_vs_one_launch.txt).
-    // (a run too long for the table's 32-bit fields -- 2^32 blocks or more -- never enters it: it goes out as the plain launch
-    // below, which cuts it into pieces of 2^26 blocks, exactly as it would on its own)
+    if ((unsigned)target > BU_TARGET_RGBA32) return BU_ERR_ARGUMENT;
     BU_HIP(ctx, hipSetDevice(ctx->device));
     unsigned long long* stw = reinterpret_cast<unsigned long long*>(d_status);
-    for (size_t r0 = 0; r0 < n_runs;) {
-        BuRunTable tb;
-        size_t k = 0, used = 0, n_tiles = 0;  // table entries, runs consumed, tiles
-        bool all_whole = true;  // every run of this launch is tiled as whole rectangles: the kernel variant without per-lane validity tests
-        const size_t bb = bu_target_block_bytes(target);
-        // BC7 / ASTC / RGBA32: a run that is whole 64 x 16-block rectangles of a power-of-two grid is tiled that way -- the caller's blocks_per_row if it is one, else (block-
-        // linear targets; RGBA32 is an image and has only its real pitch) a virtual pitch (bu_launch_uastc has the story: 16 segments of 1 KiB at >= 4 KiB pitch load faster than
-        // 16 KiB in a row; multi-run launch over 32 slices of 2^20 blocks 6.0 -> 5.6 us per slice; RGBA32 14.8 -> 12.9: profiles/r06_ab_rgba_multi_run_rectangles.txt).
-        // *whole_pitch = the pitch n blocks are whole rectangles of (0: none); returns the largest pitch of the list with at least `min_rows16` tile rows in n (ragged runs: their
-        // whole PREFIX goes out as an entry of its own, the remainder as strips -- RGBA32 only: 64 ragged images of 1021 x 1024 blocks 15.0 -> 13.1 us per image, BC7 / ASTC unmoved:
-        // profiles/r06_ab_rgba_multi_run_rectangles.txt)
-        const bool rect_target = target == BU_TARGET_BC7 || target == BU_TARGET_ASTC || target == BU_TARGET_RGBA32;
-        const size_t real = (blocks_per_row >= 128 && (blocks_per_row & (blocks_per_row - 1)) == 0 && blocks_per_row <= ((size_t)1 << 20)) ? blocks_per_row : 0;
-        const size_t pitches[5] = {real, target == BU_TARGET_RGBA32 ? (size_t)0 : (size_t)1024, target == BU_TARGET_RGBA32 ? (size_t)0 : (size_t)2048,
-                                   target == BU_TARGET_RGBA32 ? (size_t)0 : (size_t)512, target == BU_TARGET_RGBA32 ? (size_t)0 : (size_t)256};
-        auto shift_of = [](size_t v) {
-            uint32_t sh = 0;
-            while (((size_t)BU_RECT_W << sh) < v) sh++;
-            return sh;
-        };
-        // ETC1 / ETC2 batches of 2^20 blocks or more in runs long enough for them: 2048-block tiles, ONE tile per workgroup, dealt by the hardware dispatcher (512 x 4 under the
-        // shared shape's launch bounds, two resident per CU) -- what the plain launch does from 2^20 blocks on (bu_launch_sorted): 64 slices of 2^20 blocks in separate
-        // allocations 13.8 / 17.5 -> see profiles/r06_ab_etc_one_tile_workgroups.txt.  (Many short runs keep 1024-block tiles: a run's last tile is partly empty.)
-        size_t tile = 1024;
-        if (target == BU_TARGET_ETC1 || target == BU_TARGET_ETC2) {
-            size_t total = 0, tiles2 = 0;
-            for (size_t i = r0; i < n_runs && i < r0 + BU_MULTI_RUNS; i++) {
-                total += runs[i].n;
-                tiles2 += (runs[i].n + 2047) / 2048;
-            }
-            if (total >= ((size_t)1 << 20) && tiles2 * 2048 <= total + total / 8) tile = 2048;
-        }
-        auto emit = [&](const uint8_t* in, uint8_t* out, uint64_t base, size_t n, uint32_t vshift) {
-            all_whole = all_whole && vshift != BU_RUN_STRIPS;
-            tb.run[k] = BuRunDesc{reinterpret_cast<const uint4*>(in), out, base, (uint32_t)n, vshift};
-            tb.first_tile[k] = (uint32_t)n_tiles;
-            n_tiles += (n + tile - 1) / tile;
-            k++;
-        };
-        for (; r0 + used < n_runs && k < BU_MULTI_RUNS; used++) {
-            const BuRun& r = runs[r0 + used];
-            const size_t t = (r.n + tile - 1) / tile;
-            if (n_tiles + t + 1 >= (((size_t)1 << 32) / tile)) break;  // (tiles x tile size is the launch's 32-bit block count)
-            size_t whole_pitch = 0, prefix_pitch = 0;
-            if (rect_target) {
-                for (const size_t v : pitches)
-                    if (v && r.n % (16 * v) == 0) {
-                        whole_pitch = v;
-                        break;
-                    }
-                if (!whole_pitch && target == BU_TARGET_RGBA32 && k + 2 <= BU_MULTI_RUNS)  // (BC7 / ASTC gain nothing from the split: 5.95 / 6.3 us per slice either way)
-                    for (const size_t v : pitches)
-                        if (v && r.n >= 8 * 16 * v) {  // (at least eight tile rows of rectangles, or the split is not worth an entry)
-                            prefix_pitch = v;
-                            break;
-                        }
-            }
-            if (whole_pitch) {
-                emit(r.in, r.out, r.base, r.n, shift_of(whole_pitch));
-            } else if (prefix_pitch) {
-                const size_t prefix = r.n / (16 * prefix_pitch) * (16 * prefix_pitch);
-                emit(r.in, r.out, r.base, prefix, shift_of(prefix_pitch));
-                emit(r.in + prefix * 16, r.out + prefix * bb, r.base + prefix, r.n - prefix, BU_RUN_STRIPS);
-            } else {
-                emit(r.in, r.out, r.base, r.n, BU_RUN_STRIPS);
-            }
-        }
-        if (used <= 1) {  // a run on its own (the last one of a long batch, or one of 2^32 blocks): the plain launch
-            bu_status st = bu_launch_uastc(ctx, target, runs[r0].in, runs[r0].n, runs[r0].out, blocks_per_row, runs[r0].base, d_status, s, 0, policy);
+    const unsigned cu_count = (unsigned)ctx->cu_count;
+    const size_t bb = bu_target_block_bytes(target);
+    std::vector<BuRunsLaunch> plan;
+    bu_plan_runs(target, runs, n_runs, blocks_per_row, cu_count, plan);
+    for (BuRunsLaunch& l : plan) {
+        if (l.plain_run != SIZE_MAX) {
+            const BuRun& r = runs[l.plain_run];
+            const bu_status st = bu_launch_uastc(ctx, target, r.in, r.n, r.out, blocks_per_row, r.base, d_status, s, 0, policy);
             if (st) return st;
-            r0 += 1;
             continue;
         }
-        for (size_t i = k; i < BU_MULTI_RUNS + 32; i++) tb.first_tile[i] = 0xFFFFFFFFu;
-        for (size_t i = k; i < BU_MULTI_RUNS; i++) tb.run[i] = BuRunDesc{nullptr, nullptr, 0, 0u, BU_RUN_STRIPS};
-        // Shapes, as the plain launcher picks them by size (bu_context.hpp): at most one tile per CU 1024 threads on it; beyond that 512 x 2.
-        // BC7 / ASTC / RGBA32 batches of more tiles than fit the chip at once run as a PERSISTENT grid (four / four / two workgroups per CU)
-        // whose workgroups walk the tiles of all runs with the next tile's loads in flight -- a batch of large slices in separate
-        // allocations is then one long launch that overlaps its own loads and compute (two 2^20-block slices 7.9 us each, eight 6.4, against
-        // 8.4 for plain launches one after another and 9.2-10.2 through the round-4 table kernel without the prefetch).  ETC1 / ETC2 walk the same way with
-        // TWO workgroups per CU (97 / 119 VGPRs: 16 waves are what fits): 64 slices of 2^20 blocks in separate allocations 15.4 / 19.4 -> 13.8 / 17.5 us per
-        // slice against one-tile workgroups dealt by the dispatcher (tools/exp/etc_multi_persist.sh; their plain large shape sorts 4096-block tiles, the
-        // table numbers 1024-block ones: 13.4 / 17.1 when the slices are adjacent and merge into one run).
-        const bool one_per_cu = tile == 1024 && n_tiles <= (size_t)ctx->cu_count;
-        // Launch policy of a grouped launch.  Under the shared policy (launches of other streams run beside this one: bu_uastc_transcode_batch_in_flight
-        // with groups of small runs) the PERSISTENT grid is capped at about half of every CU -- two workgroups of 512 threads for BC7 / ASTC (16 of the 32 wave
-        // slots, 56 of the 160 KiB; four of 256 in the whole-tile shape below), one for RGBA32 -- so that two such launches fit side by side (ETC1 / ETC2: one of the two that fit; 64 slices of
-        // 65 536 blocks on four streams 66.3 / 80.2 -> 65.0 / 78.0 us, tools/exp/etc_small_slices.sh); the one-tile-per-CU shape is the same under both
-        // policies (a tile's 1024 threads cannot be halved).
         int pol = policy < 0 ? ctx->launch_policy.load(std::memory_order_relaxed) : policy;
-        if (pol == BU_POLICY_AUTO) pol = one_per_cu ? (int)BU_POLICY_EXCLUSIVE : bu_auto_policy(ctx, s);
-        const bool half = pol == BU_POLICY_SHARED || pol == BU_POLICY_SHARED_FEW;
-        auto go = [&](auto tgt) {
-            constexpr int T = decltype(tgt)::value;
-            constexpr bool PERSIST = true, ETC = T == BU_TGT_ETC1 || T == BU_TGT_ETC2;
-            // BC7 / ASTC batches whose runs are all whole rectangular tiles (the variant without validity tests): 256 x 4, FIVE workgroups per CU (63 / 76 VGPRs, 31 / 27 KiB),
-            // four under the shared policy.  ASTC's 512 x 2 form of that variant sits at exactly 64 VGPRs -- the compiler gets there by serialising -- and ran 64 atlases in
-            // separate allocations at 5.95-6.0 us per atlas where the plain kernel does 5.5: 5.59-5.63 in this shape (64 / 512 slices of 65 536 blocks 32.8 / 243 -> 30.6 / 219 us);
-            // BC7 5.57-5.75 -> 5.52-5.57, 512 small slices 224 -> 215 (in flight 202 -> 191): profiles/r06_ab_multi_run_256x4.txt.  Everything else 512 x 2, four / two per CU.
-            constexpr bool WHOLE_T = T == BU_TGT_BC7 || T == BU_TGT_ASTC;
-            const bool whole = WHOLE_T && all_whole;
-            const size_t cap = (size_t)ctx->cu_count * (T == BU_TGT_RGBA ? (half ? 1 : 2) : ETC ? (half ? 1 : 2) : whole ? (half ? 4 : 5) : (half ? 2 : 4));
-            const unsigned grid = (unsigned)(n_tiles < cap ? n_tiles : cap);
-            // tile tickets for the long walks of a persistent grid that has the chip to itself, as bu_go_big (a batch of 64 slices of 2^20 blocks in
-            // separate allocations: 64 tiles per workgroup)
-            unsigned* const ticket = (PERSIST && !half && n_tiles >= BU_TICKET_MIN_WALK * (size_t)grid) ? bu_ticket_for(ctx, s) : nullptr;
-            if (ETC && tile == 2048) {
-                if constexpr (ETC)
-                    hipLaunchKernelGGL((bu_uastc_multi_kernel<T, 512, 4>), dim3((unsigned)n_tiles), dim3(512), 0, s, tb, (unsigned)n_tiles, (unsigned)blocks_per_row, stw, ctx->d_tables,
-                                       (unsigned*)nullptr);
-            } else if (one_per_cu)
-                hipLaunchKernelGGL((bu_uastc_multi_kernel<T, 1024, 1>), dim3(grid), dim3(1024), 0, s, tb, (unsigned)n_tiles, (unsigned)blocks_per_row, stw, ctx->d_tables, (unsigned*)nullptr);
-            else if (whole) {
-                if constexpr (WHOLE_T)
-                    hipLaunchKernelGGL((bu_uastc_multi_kernel<T, 256, 4, PERSIST, true>), dim3(grid), dim3(256), 0, s, tb, (unsigned)n_tiles, (unsigned)blocks_per_row, stw, ctx->d_tables, ticket);
-            } else
-                hipLaunchKernelGGL((bu_uastc_multi_kernel<T, 512, 2, PERSIST>), dim3(grid), dim3(512), 0, s, tb, (unsigned)n_tiles, (unsigned)blocks_per_row, stw, ctx->d_tables, ticket);
-        };
-        switch (target) {
-        case BU_TARGET_ASTC: go(std::integral_constant<int, BU_TGT_ASTC>()); break;
-        case BU_TARGET_BC7: go(std::integral_constant<int, BU_TGT_BC7>()); break;
-        case BU_TARGET_ETC1: go(std::integral_constant<int, BU_TGT_ETC1>()); break;
-        case BU_TARGET_ETC2: go(std::integral_constant<int, BU_TGT_ETC2>()); break;
-        default: go(std::integral_constant<int, BU_TGT_RGBA>()); break;
+        if (pol == BU_POLICY_AUTO) pol = l.needs_policy ? bu_auto_policy(ctx, s) : (int)BU_POLICY_EXCLUSIVE;
+        bu_plan_multi_kernel(target, pol, cu_count, l);
+        BuRunTable tb;
+        for (size_t i = 0; i < l.k; i++) {
+            const BuRunEntry& e = l.entries[i];
+            const BuRun& r = runs[e.run];
+            tb.run[i] = BuRunDesc{reinterpret_cast<const uint4*>(r.in + e.offset * 16), r.out + e.offset * bb, r.base + e.offset, (uint32_t)e.n, e.vshift};
+            tb.first_tile[i] = e.first_tile;
         }
+        for (size_t i = l.k; i < BU_MULTI_RUNS + 32; i++) tb.first_tile[i] = 0xFFFFFFFFu;
+        for (size_t i = l.k; i < BU_MULTI_RUNS; i++) tb.run[i] = BuRunDesc{nullptr, nullptr, 0, 0u, BU_RUN_STRIPS};
+        const BuMultiFn k = bu_multi_kernels[target][l.kernel];
+        if (!k) return BU_ERR_ARGUMENT;
+        unsigned* const ticket = l.wants_ticket ? bu_ticket_for(ctx, s) : nullptr;
+        hipLaunchKernelGGL(k, dim3(l.grid), dim3(l.block), 0, s, tb, (unsigned)l.n_tiles, (unsigned)blocks_per_row, stw, ctx->d_tables, ticket);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return bu_fail(ctx, e, "multi-run launch");
-        r0 += used;
     }
     return BU_OK;
 }

@@ -19,18 +19,22 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <future>
+#include <iterator>
 #include <mutex>
 #include <new>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/basisu_hip.h"
 #include "bu_basis.hpp"
 #include "bu_batch_plan.hpp"   // slices -> runs -> launches of the batch entry points (host only)
 #include "bu_uastc_dispatch.hpp"
+#include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 
 #include "bu_kernels.hpp"        // device code
 #include "bu_context.hpp"        // bu_context, launcher, host-pointer driver

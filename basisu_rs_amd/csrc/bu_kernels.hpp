@@ -4,14 +4,7 @@
 #pragma once
 namespace {
 
-constexpr int BU_WG = 256;            // 4 waves
-// Below this the plain one-lane-per-block kernel is used.  It runs one mode path per DISTINCT mode present, so it only
-// wins for a handful of blocks (BC7: 1 block 2.3 vs 3.3 us, 8 blocks 4.2 vs 3.7 us, 64 blocks 7.8 vs 4.4 us,
-// 1024 blocks 16.1 vs 4.8 us; ETC1 at 128 blocks 38.6 vs 15.0 us).
-constexpr int BU_SORT_MIN_BLOCKS = 8;
-// shapes of the mode-sorted kernel whose tile size is a run-time argument (bu_balanced_tile): ETC1 / ETC2 on 4096-block tiles
-constexpr bool bu_dyn_tile(int target, int tile) { return (target == BU_TGT_ETC1 || target == BU_TGT_ETC2) && tile == 4096; }
-
+// (BU_WG, BU_SORT_MIN_BLOCKS, bu_dyn_tile, BU_RECT_W, BU_MULTI_RUNS, BU_RUN_STRIPS: bu_launch_plan.hpp)
 // ------------------------------------------------------------------------------------------------
 // LDS image of the tables of TARGET: [BuBc7Tables (BC7 only)][BuTables up to the end of the target's ranges]
 constexpr unsigned bu_lds_front(int target) { return target == 1 ? (unsigned)sizeof(BuBc7Tables) : 0u; }
@@ -174,8 +167,7 @@ __device__ __forceinline__ uint32_t bu_scan32(uint32_t v)
 // filled chunks (mode-coherent atlas: BC7 -5...-10 %).  64 blocks wide: a wave's load / store instruction is still one contiguous
 // KiB (32-wide tiles, two 512-byte segments per instruction, cost the uniform-random atlas +3 % on BC7).  Nothing else changes (the
 // sort works on the index inside the tile).  A compile-time variant: as a run-time switch the extra index arithmetic cost the
-// strip path 4 % (round 2).
-constexpr unsigned BU_RECT_W = 64;
+// strip path 4 % (round 2).  BU_RECT_W = 64.
 // MULTI (LAYOUT 2): the launch covers SEVERAL runs of blocks at unrelated addresses (slices of a texture array in separate
 // allocations); tiles never straddle runs.  The run table travels IN THE KERNEL ARGUMENTS (bu_uastc_multi_kernel: no device
 // buffer, no copy, nothing to free behind the launch): per run its input, output, block-index base, size and the number of its
@@ -190,8 +182,6 @@ struct BuRunDesc {
     uint32_t vshift;  // BU_RUN_STRIPS: tiles are strips of 1024 consecutive blocks; else the run is whole 64 x 16-block rectangles of a (virtual) grid
                       // 64 << vshift blocks wide (bu_launch_runs: a power of two, the run a multiple of 16 rows of it)
 };
-constexpr unsigned BU_MULTI_RUNS = 96;
-constexpr uint32_t BU_RUN_STRIPS = 0xFFFFFFFFu;
 struct BuRunTable {
     BuRunDesc run[BU_MULTI_RUNS];
     uint32_t first_tile[BU_MULTI_RUNS + 32];  // ascending; entries past the last run hold 0xFFFFFFFF (128 entries: two 64-lane loads)
@@ -1007,18 +997,6 @@ __global__ __launch_bounds__(BU_WG) void bu_etc1s_file_kernel(const uint32_t* __
             for (int r = 0; r < 4; r++) bu_st_stream(img + (size_t)(4 * by + r) * sd.nbx + bx, make_uint4(px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]));
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-unsigned bu_grid_for(size_t n_blocks, int cu_count)
-{
-    // enough workgroups to fill the chip several times over, capped so every workgroup amortises its
-    // table copy over >= 2 batches on large inputs (guide: grid ~ CUs x 8 for memory-bound kernels)
-    size_t wgs = (n_blocks + BU_WG - 1) / BU_WG;
-    const size_t cap = (size_t)cu_count * 8;
-    if (wgs > cap) wgs = cap;
-    if (wgs == 0) wgs = 1;
-    return (unsigned)wgs;
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 // library and nothing under basisu_rs_amd/ loads it.
 #include "bu_uastc_dispatch.hpp"
 #include "bu_batch_plan.hpp"
+#include "bu_launch_plan.hpp"
 
 static BuTablesAll g_tables;
 static bool g_init = false;
@@ -76,5 +77,52 @@ size_t bu_emul_plan_in_flight(size_t n_slices, const uint64_t* in_addr, const si
         }
     if (out_launches) *out_launches = groups.size();
     return n;
+}
+// the launches of bu_launch_uastc for one slice (bu_plan_slice): BU_POLICY_AUTO stands for `auto_result` where the launcher would ask bu_auto_policy.
+// Rows of 15: offset, n, kernel (-1: the one-lane-per-block kernel), its WGS, BPT, MINW, PREFETCH, RECT, grid, block, tile_rt, rect_magic, cus, bpr,
+// wants_ticket; returns the number of launches (or the number needed if `cap` is too small), *needs_policy = bu_slice_needs_policy
+size_t bu_emul_launch_plan(int target, size_t n_blocks, size_t bpr, unsigned grid_cap, int policy, int auto_result, unsigned cu_count, int64_t* rows, size_t cap,
+                           int* needs_policy)
+{
+    *needs_policy = bu_slice_needs_policy(n_blocks, grid_cap, cu_count);
+    if (policy == BU_POLICY_AUTO) policy = *needs_policy ? auto_result : (int)BU_POLICY_EXCLUSIVE;
+    std::vector<BuSliceLaunch> plan;
+    bu_plan_slice(target, n_blocks, bpr, grid_cap, policy, cu_count, plan);
+    for (size_t i = 0; i < plan.size() && i < cap; i++) {
+        const BuSliceLaunch& l = plan[i];
+        const BuSortedKey k = l.kernel < 0 ? BuSortedKey{target, 0, 0, 0, false, false} : BU_SORTED_KERNELS[l.kernel];
+        const int64_t r[15] = {(int64_t)l.offset, (int64_t)l.n, l.kernel, k.wgs, k.bpt, k.minw, k.prefetch, k.rect, l.grid, l.block, l.tile_rt, l.rect_magic, l.cus,
+                               (int64_t)l.bpr, l.wants_ticket};
+        memcpy(rows + 15 * i, r, sizeof(r));
+    }
+    return plan.size();
+}
+// the launches of bu_launch_runs (bu_plan_runs, then bu_plan_multi_kernel under `policy`, AUTO as above) for runs given as ADDRESSES.  Rows of 10 per launch:
+// plain_run (-1: multi-run launch), k, n_tiles, tile, needs_policy, kernel (BU_MULTI_*), grid, block, wants_ticket, index of its first entry; entries
+// rows of 5: run, offset, n, vshift, first_tile.  Returns the number of launches (0 if a table is too small).
+size_t bu_emul_runs_plan(int target, size_t n_runs, const uint64_t* in_addr, const uint64_t* out_addr, const size_t* n_blocks, const uint64_t* base, size_t bpr,
+                         int policy, int auto_result, unsigned cu_count, int64_t* rows, size_t cap, int64_t* entries, size_t entries_cap)
+{
+    std::vector<BuRun> runs;
+    for (size_t i = 0; i < n_runs; i++)
+        runs.push_back(BuRun{reinterpret_cast<const uint8_t*>(in_addr[i]), reinterpret_cast<uint8_t*>(out_addr[i]), n_blocks[i], base[i]});
+    std::vector<BuRunsLaunch> plan;
+    bu_plan_runs(target, runs.data(), n_runs, bpr, cu_count, plan);
+    size_t e = 0;
+    if (plan.size() > cap) return 0;
+    for (size_t j = 0; j < plan.size(); j++) {
+        BuRunsLaunch& l = plan[j];
+        if (l.plain_run == SIZE_MAX) bu_plan_multi_kernel(target, policy != BU_POLICY_AUTO ? policy : l.needs_policy ? auto_result : (int)BU_POLICY_EXCLUSIVE, cu_count, l);
+        const bool plain = l.plain_run != SIZE_MAX;
+        const int64_t r[10] = {plain ? (int64_t)l.plain_run : -1, (int64_t)l.k, (int64_t)l.n_tiles, l.tile, l.needs_policy, plain ? -1 : l.kernel, l.grid, l.block, l.wants_ticket, (int64_t)e};
+        memcpy(rows + 10 * j, r, sizeof(r));
+        if (e + l.k > entries_cap) return 0;
+        for (size_t i = 0; i < l.k; i++, e++) {
+            const BuRunEntry& x = l.entries[i];
+            const int64_t er[5] = {(int64_t)x.run, (int64_t)x.offset, (int64_t)x.n, x.vshift, x.first_tile};
+            memcpy(entries + 5 * e, er, sizeof(er));
+        }
+    }
+    return plan.size();
 }
 }

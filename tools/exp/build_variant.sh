@@ -2,7 +2,7 @@
 # tools/exp/build_variant.sh NAME [--sed EXPR]... [-DFLAG ...]  ->  tools/exp/lib_NAME.so
 # A whole-library variant for A/B runs (tools/exp/ab_multi.py, ab_streams.py).  The shipped sources carry no experiment switches: a variant
 # that changes code is built from a scratch COPY of basisu_rs_amd/csrc + include/ edited with the given sed expressions (applied to every file),
-# e.g.  build_variant.sh bc7half --sed 's/BuBigShape<BU_TGT_BC7, BU_POLICY_SHARED> : BuShape<256, 4, 1, true, true, 2>/BuBigShape<BU_TGT_BC7, BU_POLICY_SHARED> : BuShape<512, 2, 1, true, true, 2>/'
+# e.g.  build_variant.sh walk8 --sed 's/BU_TICKET_MIN_WALK = 16/BU_TICKET_MIN_WALK = 8/'  (a new shape also needs its line in BU_SORTED_KERNELS)
 name=$1; shift
 seds=()
 while [ "$1" = "--sed" ]; do seds+=(-e "$2"); shift 2; done
