@@ -17,7 +17,11 @@ from .api import (  # noqa: F401
     read_query,
     read_slice_descs,
     read_to_astc,
+    read_to_bc4,
+    read_to_bc5,
     read_to_bc7,
+    read_to_eac_r11,
+    read_to_eac_rg11,
     read_to_etc1,
     read_to_etc2,
     read_to_rgba,

@@ -36,6 +36,11 @@ class TargetTextureFormat(enum.IntEnum):  # uastc.rs:41-47
     Bc7 = _lib.BC7
     Etc1 = _lib.ETC1
     Etc2 = _lib.ETC2
+    # one- and two-channel targets (no counterpart in the reference; include/basisu_hip.h): two channels take X = R, Y = A
+    Bc4R = _lib.BC4_R
+    Bc5Rg = _lib.BC5_RG
+    EacR11 = _lib.EAC_R11
+    EacRg11 = _lib.EAC_RG11
 
 
 def _as_u8(data):
@@ -364,6 +369,22 @@ def read_to_astc(buf, ctx=None, out=None):  # basis.rs:204-231
 
 def read_to_bc7(buf, ctx=None, out=None):  # basis.rs:233-260
     return _read_to(_lib.READ_BC7, buf, ctx, out)[1]
+
+
+def read_to_bc4(buf, ctx=None, out=None):  # UASTC files only: BC4 of R
+    return _read_to(_lib.READ_BC4, buf, ctx, out)[1]
+
+
+def read_to_bc5(buf, ctx=None, out=None):  # UASTC files only: BC5 of R, A
+    return _read_to(_lib.READ_BC5, buf, ctx, out)[1]
+
+
+def read_to_eac_r11(buf, ctx=None, out=None):  # UASTC files only: EAC R11 of R
+    return _read_to(_lib.READ_EAC_R11, buf, ctx, out)[1]
+
+
+def read_to_eac_rg11(buf, ctx=None, out=None):  # UASTC files only: EAC RG11 of R, A
+    return _read_to(_lib.READ_EAC_RG11, buf, ctx, out)[1]
 
 
 def basislz_decode(buf, slice_index=None):

@@ -32,6 +32,22 @@ using bu_host::BuFilePlan;
 using bu_host::bu_plan_file;
 using bu_host::bu_make_lz;
 
+// the slice-level target a UASTC file's slices are transcoded to (BU_READ_UASTC never gets here: plain copies)
+static bu_target bu_read_block_target(bu_read_target target)
+{
+    switch (target) {
+    case BU_READ_RGBA: return BU_TARGET_RGBA32;
+    case BU_READ_ASTC: return BU_TARGET_ASTC;
+    case BU_READ_BC7: return BU_TARGET_BC7;
+    case BU_READ_ETC1: return BU_TARGET_ETC1;
+    case BU_READ_BC4: return BU_TARGET_BC4_R;
+    case BU_READ_BC5: return BU_TARGET_BC5_RG;
+    case BU_READ_EAC_R11: return BU_TARGET_EAC_R11;
+    case BU_READ_EAC_RG11: return BU_TARGET_EAC_RG11;
+    default: return BU_TARGET_ETC2;
+    }
+}
+
 static bu_status bu_read_query_impl(bu_read_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes)
 {
     BuFilePlan p;
@@ -728,8 +744,7 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
                         BU_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));  // the status words are reset on the context stream
                         for (; used_extra < n_ps - 1; used_extra++) BU_HIP(ctx, hipStreamWaitEvent(ctx->extra_streams[used_extra], ctx->ev0, 0));
                     }
-                    const bu_target pbt = target == BU_READ_ASTC ? BU_TARGET_ASTC : target == BU_READ_BC7 ? BU_TARGET_BC7
-                                          : target == BU_READ_ETC1 ? BU_TARGET_ETC1 : BU_TARGET_ETC2;
+                    const bu_target pbt = bu_read_block_target(target);
                     const size_t obytes = bu_target_block_bytes(pbt);
                     size_t piece_no = 0;
                     for (size_t done = 0; done < run_bytes; done += piece_bytes, piece_no++) {
@@ -747,11 +762,7 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
                     crc_enqueue(d_in + in_off[k], s.file_ofs, run_bytes, ctx->stream);
                 }
             }
-            const bu_target bt = target == BU_READ_RGBA ? BU_TARGET_RGBA32
-                                 : target == BU_READ_ASTC ? BU_TARGET_ASTC
-                                 : target == BU_READ_BC7  ? BU_TARGET_BC7
-                                 : target == BU_READ_ETC1 ? BU_TARGET_ETC1
-                                                          : BU_TARGET_ETC2;
+            const bu_target bt = bu_read_block_target(target);
             if (target == BU_READ_RGBA) {  // image geometry differs per slice: one launch each
                 st = bu_launch_uastc(ctx, bt, d_in + in_off[k], s.file_size / 16, d_out + im.offset, s.num_blocks_x ? s.num_blocks_x : 1, 0, d_status + k,
                                      ctx->stream, direct_out ? BU_ZEROCOPY_GRID : 0);

@@ -8,8 +8,12 @@ size_t bu_target_block_bytes(bu_target target)
     switch (target) {
     case BU_TARGET_ASTC:
     case BU_TARGET_BC7:
-    case BU_TARGET_ETC2: return 16;
-    case BU_TARGET_ETC1: return 8;
+    case BU_TARGET_ETC2:
+    case BU_TARGET_BC5_RG:
+    case BU_TARGET_EAC_RG11: return 16;
+    case BU_TARGET_ETC1:
+    case BU_TARGET_BC4_R:
+    case BU_TARGET_EAC_R11: return 8;
     case BU_TARGET_RGBA32: return 64;
     default: return 0;
     }
@@ -213,7 +217,7 @@ bu_status bu_launch_runs(bu_context* ctx, bu_target target, const BuRun* runs, s
 {
     if (n_runs == 0) return BU_OK;
     if (n_runs == 1) return bu_launch_uastc(ctx, target, runs[0].in, runs[0].n, runs[0].out, blocks_per_row, runs[0].base, d_status, s, 0, policy);
-    if ((unsigned)target > BU_TARGET_RGBA32) return BU_ERR_ARGUMENT;
+    if (bu_target_block_bytes(target) == 0) return BU_ERR_ARGUMENT;
     BU_HIP(ctx, hipSetDevice(ctx->device));
     unsigned long long* stw = reinterpret_cast<unsigned long long*>(d_status);
     const unsigned cu_count = (unsigned)ctx->cu_count;

@@ -85,7 +85,7 @@ __device__ __forceinline__ void bu_st_stream(uint2* p, const uint2 v)
 #endif
 }
 
-// UASTC -> {ASTC, BC7, ETC1, ETC2, RGBA32}: replaces the loop of uastc.rs:157-165 / 96-107
+// UASTC -> {ASTC, BC7, ETC1, ETC2, RGBA32, BC4, BC5, EAC R11, EAC RG11}: replaces the loop of uastc.rs:157-165 / 96-107
 template <int TARGET>
 __global__ __launch_bounds__(BU_WG) void bu_uastc_kernel(const uint4* __restrict__ in, void* __restrict__ out, size_t n_blocks,
                                                          unsigned bpr, unsigned long long base, unsigned long long* status,
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(BU_WG) void bu_uastc_kernel(const uint4* __restrict
 #pragma unroll
             for (int i = 0; i < (TARGET == BU_TGT_RGBA ? 16 : 4); i++) o[i] = 0;
         }
-        if constexpr (TARGET == BU_TGT_ETC1) {
+        if constexpr (bu_out_words(TARGET) == 2) {  // ETC1, BC4, EAC R11
             reinterpret_cast<uint2*>(out)[idx] = make_uint2(o[0], o[1]);
         } else if constexpr (TARGET == BU_TGT_RGBA) {
             const size_t by = idx / bpr, bx = idx - by * bpr;
@@ -386,7 +386,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             tv[k] = i < TVT ? tsrc[tdst(i)] : make_uint4(0, 0, 0, 0);
         }
         static_assert(offsetof(BuTables, key_lut) % 4 == 0 && sizeof(T.key_lut[0]) == 128, "the target's key_lut is staged as 32 dwords");
-        if (tid < 32) reinterpret_cast<uint32_t*>(T.key_lut[TARGET])[tid] = reinterpret_cast<const uint32_t*>(tables->t.key_lut[TARGET])[tid];
+        if (tid < 32) reinterpret_cast<uint32_t*>(T.key_lut[bu_cost_row(TARGET)])[tid] = reinterpret_cast<const uint32_t*>(tables->t.key_lut[bu_cost_row(TARGET)])[tid];
     }
     bool tables_staged = !SPLIT;
     if (tid < 64) (&cnt[0][0])[tid] = 0;
@@ -408,7 +408,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
             const bool valid = WHOLE || (MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
-            key[j] = valid ? T.key_lut[TARGET][v[j].x & 127u] : 31u;
+            key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
             uniform = uniform && (__ballot(key[j] == (uint32_t)__builtin_amdgcn_readfirstlane(key[j])) == ~0ull) && has_block(key[j]);
         }
         if (uniform) {
@@ -492,7 +492,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             if (active) {
                 switch (r) {  // the run number IS the sort key: run k holds mode BU_COST_ORDER[k] (run 19: invalid mode codes)
 #define BU_CASE(k) \
-    case k: st = bu_block_mode<TARGET, BU_COST_ORDER[TARGET][k]>(T, b, o); break;
+    case k: st = bu_block_mode<TARGET, BU_COST_ORDER[bu_cost_row(TARGET)][k]>(T, b, o); break;
                     BU_CASE(0) BU_CASE(1) BU_CASE(2) BU_CASE(3) BU_CASE(4) BU_CASE(5) BU_CASE(6) BU_CASE(7) BU_CASE(8) BU_CASE(9)
                     BU_CASE(10) BU_CASE(11) BU_CASE(12) BU_CASE(13) BU_CASE(14) BU_CASE(15) BU_CASE(16) BU_CASE(17) BU_CASE(18)
 #undef BU_CASE
@@ -547,7 +547,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
                     for (int r = 0; r < 4; r++) bu_st_stream(img + (size_t)((4 * by + r) * bpr + bx), sout[r * BU_TILE + dest[j]]);
                 } else {
                     const uint4 r = sblk[dest[j]];
-                    if constexpr (TARGET == BU_TGT_ETC1) bu_st_stream(reinterpret_cast<uint2*>(out) + idx, make_uint2(r.x, r.y));
+                    if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out) + idx, make_uint2(r.x, r.y));
                     else bu_st_stream(reinterpret_cast<uint4*>(out) + idx, r);
                 }
             }
@@ -590,8 +590,8 @@ __global__ __launch_bounds__(WGS, MINW) void bu_uastc_sorted_kernel(const uint4*
 // WHOLE: every run of the table is tiled as whole rectangles (the host checked: BuRunDesc::vshift of all of them)
 // (ASTC, 512 threads: the register allocation is held to the 64 VGPRs at which FOUR such workgroups fit a CU -- left alone it takes 66, three fit, and a persistent grid of four
 //  per CU runs its fourth behind the others: 64 ragged slices of ~2^20 blocks 6.7 -> see profiles/r06_ab_astc_64_vgprs.txt)
-// (ETC1 / ETC2 also as 512 x 4 on 2048-block tiles -- the host then numbers 2048-block tiles -- under the shared shape's __launch_bounds__(512, 4): two workgroups per CU)
-constexpr bool bu_multi_etc_2048(int target, int tile) { return (target == BU_TGT_ETC1 || target == BU_TGT_ETC2) && tile == 2048; }
+// (ETC1 / ETC2 and the channel targets also as 512 x 4 on 2048-block tiles -- the host then numbers 2048-block tiles -- under the shared shape's __launch_bounds__(512, 4): two workgroups per CU)
+constexpr bool bu_multi_etc_2048(int target, int tile) { return bu_etc_family(target) && tile == 2048; }
 template <int TARGET, int WGS, int BPT, bool PREFETCH = false, bool WHOLE = false>
 __global__ __launch_bounds__(WGS, (TARGET == BU_TGT_ASTC && WGS == 512) ? 8 : bu_multi_etc_2048(TARGET, WGS * BPT) ? 4 : 1) void bu_uastc_multi_kernel(
     const BuRunTable table, unsigned n_tiles, unsigned bpr, unsigned long long* status, const BuTablesAll* __restrict__ tables, unsigned* __restrict__ ticket)

@@ -15,8 +15,8 @@ constexpr int BU_WG = 256;            // 4 waves
 // wins for a handful of blocks (BC7: 1 block 2.3 vs 3.3 us, 8 blocks 4.2 vs 3.7 us, 64 blocks 7.8 vs 4.4 us,
 // 1024 blocks 16.1 vs 4.8 us; ETC1 at 128 blocks 38.6 vs 15.0 us).
 constexpr int BU_SORT_MIN_BLOCKS = 8;
-// shapes of the mode-sorted kernel whose tile size is a run-time argument (bu_balanced_tile): ETC1 / ETC2 on 4096-block tiles
-constexpr bool bu_dyn_tile(int target, int tile) { return (target == BU_TGT_ETC1 || target == BU_TGT_ETC2) && tile == 4096; }
+// shapes of the mode-sorted kernel whose tile size is a run-time argument (bu_balanced_tile): the ETC family on 4096-block tiles
+constexpr bool bu_dyn_tile(int target, int tile) { return bu_etc_family(target) && tile == 4096; }
 constexpr unsigned BU_RECT_W = 64;  // width of a rectangular tile (bu_kernels.hpp, layout RECT)
 constexpr unsigned BU_MULTI_RUNS = 96;  // runs per multi-run launch (bu_kernels.hpp, BuRunTable)
 constexpr uint32_t BU_RUN_STRIPS = 0xFFFFFFFFu;
@@ -117,6 +117,13 @@ constexpr BuSortedKey BU_SORTED_KERNELS[] = {
     {BU_TGT_ETC2, 1024, 1, 1, false, false}, {BU_TGT_ETC2, 512, 2, 1, false, false}, {BU_TGT_ETC2, 1024, 4, 1, true, false}, {BU_TGT_ETC2, 1024, 4, 1, true, true},
     {BU_TGT_ETC2, 512, 4, 4, false, false}, {BU_TGT_ETC2, 512, 4, 4, false, true}, {BU_TGT_ETC2, 256, 4, 1, true, false}, {BU_TGT_ETC2, 256, 4, 1, true, true},
     {BU_TGT_RGBA, 1024, 1, 1, true, false}, {BU_TGT_RGBA, 1024, 1, 1, true, true}, {BU_TGT_RGBA, 512, 2, 1, true, false}, {BU_TGT_RGBA, 512, 2, 1, true, true},
+// the one- and two-channel targets: the ETC shapes they are planned in (bu_shape_target) -- one tile per CU, the mid shape, the exclusive and the
+// shared large shapes (strips and rectangles), the zero-copy shape
+#define BU_CHANNEL_SHAPES(T, SHARED_PREFETCH)                                                                                                   \
+    {T, 1024, 1, 1, false, false}, {T, 512, 2, 1, false, false}, {T, 1024, 4, 1, true, false}, {T, 1024, 4, 1, true, true},                     \
+    {T, 512, 4, 4, SHARED_PREFETCH, false}, {T, 512, 4, 4, SHARED_PREFETCH, true}, {T, 256, 4, 1, true, false}
+    BU_CHANNEL_SHAPES(BU_TGT_BC4, true), BU_CHANNEL_SHAPES(BU_TGT_BC5, false), BU_CHANNEL_SHAPES(BU_TGT_R11, true), BU_CHANNEL_SHAPES(BU_TGT_RG11, false),
+#undef BU_CHANNEL_SHAPES
 };
 constexpr int bu_sorted_kernel(int target, const BuShape& s, bool rect)
 {
@@ -155,8 +162,10 @@ inline bool bu_slice_needs_policy(size_t n_blocks, unsigned grid_cap, unsigned c
 
 // The launches of one slice of n_blocks blocks (blocks_per_row: the caller's block grid, 0 = unknown) under the resolved `policy` (BU_POLICY_*, not AUTO).
 // grid_cap > 0 (zero-copy over PCIe): 1024-block tiles on at most grid_cap workgroups.
-inline void bu_plan_slice(int target, size_t n_blocks, size_t bpr, unsigned grid_cap, int policy, unsigned cu_count, std::vector<BuSliceLaunch>& out)
+// (kernel_target: the slice's target, whose kernels run; every shape decision is its family's, bu_shape_target)
+inline void bu_plan_slice(int kernel_target, size_t n_blocks, size_t bpr, unsigned grid_cap, int policy, unsigned cu_count, std::vector<BuSliceLaunch>& out)
 {
+    const int target = bu_shape_target(kernel_target);
     out.clear();
     if (n_blocks == 0) return;
     if (n_blocks < (size_t)BU_SORT_MIN_BLOCKS) {
@@ -202,7 +211,7 @@ inline void bu_plan_slice(int target, size_t n_blocks, size_t bpr, unsigned grid
             // (a shape that sizes its tile at run time is rectangular only when that size is the full tile)
             const bool rect = S.rect && rect_ok && (!bu_dyn_tile(target, (int)S.tile()) || tile_rt == S.tile());
             ticket = ticket && grid_cap == 0 && grid >= BU_TICKET_MIN_GRID;
-            out.push_back(BuSliceLaunch{done, nb, bu_sorted_kernel(target, S, rect), (unsigned)grid, (unsigned)S.wgs, (unsigned)tile_rt, rect_magic, cus, bpr, ticket});
+            out.push_back(BuSliceLaunch{done, nb, bu_sorted_kernel(kernel_target, S, rect), (unsigned)grid, (unsigned)S.wgs, (unsigned)tile_rt, rect_magic, cus, bpr, ticket});
         };
         // a large launch in shape S: persistent workgroups, PER_CU per CU, walking equal shares of the tiles.  `priorities`: the static wave
         // priorities by residency generation (kernel, `cus`).  They serve a launch that is ALONE on the chip (BC7 8.57 -> 8.37 us) and hurt as
@@ -294,8 +303,9 @@ struct BuRunsLaunch {
 // of 65 536 blocks: 290 us on one stream, 230-260 us on 2-8, profiles/r03_small_slices_streams_vs_one_launch.txt).
 // (a run too long for the table's 32-bit fields -- 2^32 blocks or more -- never enters it: it goes out as the plain launch
 // below, which cuts it into pieces of 2^26 blocks, exactly as it would on its own)
-inline void bu_plan_runs(int target, const BuRun* runs, size_t n_runs, size_t blocks_per_row, unsigned cu_count, std::vector<BuRunsLaunch>& out)
+inline void bu_plan_runs(int kernel_target, const BuRun* runs, size_t n_runs, size_t blocks_per_row, unsigned cu_count, std::vector<BuRunsLaunch>& out)
 {
+    const int target = bu_shape_target(kernel_target);  // (as bu_plan_slice)
     out.clear();
     // BC7 / ASTC / RGBA32: a run that is whole 64 x 16-block rectangles of a power-of-two grid is tiled that way -- the caller's blocks_per_row if it is one, else (block-
     // linear targets; RGBA32 is an image and has only its real pitch) a virtual pitch (bu_plan_slice has the story: 16 segments of 1 KiB at >= 4 KiB pitch load faster than
@@ -385,8 +395,9 @@ inline void bu_plan_runs(int target, const BuRun* runs, size_t n_runs, size_t bl
 // slots, 56 of the 160 KiB; four of 256 in the whole-tile shape below), one for RGBA32 -- so that two such launches fit side by side (ETC1 / ETC2: one of the two that fit; 64 slices of
 // 65 536 blocks on four streams 66.3 / 80.2 -> 65.0 / 78.0 us, tools/exp/etc_small_slices.sh); the one-tile-per-CU shape is the same under both
 // policies (a tile's 1024 threads cannot be halved).
-inline void bu_plan_multi_kernel(int target, int policy, unsigned cu_count, BuRunsLaunch& l)
+inline void bu_plan_multi_kernel(int kernel_target, int policy, unsigned cu_count, BuRunsLaunch& l)
 {
+    const int target = bu_shape_target(kernel_target);  // (as bu_plan_slice)
     const bool half = policy == BU_POLICY_SHARED || policy == BU_POLICY_SHARED_FEW;
     const bool etc = target == BU_TGT_ETC1 || target == BU_TGT_ETC2;
     // BC7 / ASTC batches whose runs are all whole rectangular tiles (the variant without validity tests): 256 x 4, FIVE workgroups per CU (63 / 76 VGPRs, 31 / 27 KiB),

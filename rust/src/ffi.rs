@@ -18,6 +18,10 @@ pub const BU_TARGET_BC7: c_int = 1;
 pub const BU_TARGET_ETC1: c_int = 2;
 pub const BU_TARGET_ETC2: c_int = 3;
 pub const BU_TARGET_RGBA32: c_int = 4;
+pub const BU_TARGET_BC4_R: c_int = 6;
+pub const BU_TARGET_BC5_RG: c_int = 7;
+pub const BU_TARGET_EAC_R11: c_int = 8;
+pub const BU_TARGET_EAC_RG11: c_int = 9;
 // bu_read_target
 pub const BU_READ_RGBA: c_int = 0;
 pub const BU_READ_ETC1: c_int = 1;
@@ -25,6 +29,10 @@ pub const BU_READ_ETC2: c_int = 2;
 pub const BU_READ_UASTC: c_int = 3;
 pub const BU_READ_ASTC: c_int = 4;
 pub const BU_READ_BC7: c_int = 5;
+pub const BU_READ_BC4: c_int = 6;
+pub const BU_READ_BC5: c_int = 7;
+pub const BU_READ_EAC_R11: c_int = 8;
+pub const BU_READ_EAC_RG11: c_int = 9;
 pub const BU_OK: c_int = 0;
 pub const BU_COMM_ID_BYTES: usize = 128;
 pub const BU_IPC_HANDLE_BYTES: usize = 64;
