@@ -17,6 +17,8 @@ from .api import (  # noqa: F401
     read_query,
     read_slice_descs,
     read_to_astc,
+    read_to_bc1,
+    read_to_bc3,
     read_to_bc4,
     read_to_bc5,
     read_to_bc7,

@@ -9,7 +9,8 @@ LIB_PATH = os.environ.get("BASISU_HIP_LIB") or os.path.join(HERE, "libbasisu_hip
 # bu_target
 ASTC, BC7, ETC1, ETC2, RGBA32 = 0, 1, 2, 3, 4
 BC4_R, BC5_RG, EAC_R11, EAC_RG11 = 6, 7, 8, 9  # one- and two-channel targets (two channels: X = R, Y = A); 5 names no target
-BLOCK_BYTES = {ASTC: 16, BC7: 16, ETC1: 8, ETC2: 16, RGBA32: 64, BC4_R: 8, BC5_RG: 16, EAC_R11: 8, EAC_RG11: 16}
+BC1_RGB, BC3_RGBA = 11, 12  # colour targets (BC1 drops A; BC3 = BC4 of A + BC1); 10 names no target
+BLOCK_BYTES = {ASTC: 16, BC7: 16, ETC1: 8, ETC2: 16, RGBA32: 64, BC4_R: 8, BC5_RG: 16, EAC_R11: 8, EAC_RG11: 16, BC1_RGB: 8, BC3_RGBA: 16}
 # bu_status
 OK, ERR_INVALID_MODE, ERR_INVALID_PATTERN, ERR_LENGTH, ERR_OUTPUT_SIZE, ERR_ARGUMENT, ERR_INDEX_RANGE, ERR_NO_DEVICE, ERR_HIP = range(9)
 ERR_UNSUPPORTED, ERR_BOUNDS = 17, 19
@@ -36,6 +37,7 @@ COMM_ID_BYTES, IPC_HANDLE_BYTES = 128, 64
 # bu_read_target
 READ_RGBA, READ_ETC1, READ_ETC2, READ_UASTC, READ_ASTC, READ_BC7 = range(6)
 READ_BC4, READ_BC5, READ_EAC_R11, READ_EAC_RG11 = range(6, 10)  # UASTC files only
+READ_BC1, READ_BC3 = 11, 12  # UASTC files only; 10 names no read target
 
 
 class BasisHeader(ctypes.Structure):  # bu_basis_header == basis::Header (basis.rs:417-454)

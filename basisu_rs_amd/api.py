@@ -41,6 +41,9 @@ class TargetTextureFormat(enum.IntEnum):  # uastc.rs:41-47
     Bc5Rg = _lib.BC5_RG
     EacR11 = _lib.EAC_R11
     EacRg11 = _lib.EAC_RG11
+    # colour targets (no counterpart in the reference; include/basisu_hip.h): BC1 drops A, BC3 is BC4 of A then BC1
+    Bc1Rgb = _lib.BC1_RGB
+    Bc3Rgba = _lib.BC3_RGBA
 
 
 def _as_u8(data):
@@ -385,6 +388,14 @@ def read_to_eac_r11(buf, ctx=None, out=None):  # UASTC files only: EAC R11 of R
 
 def read_to_eac_rg11(buf, ctx=None, out=None):  # UASTC files only: EAC RG11 of R, A
     return _read_to(_lib.READ_EAC_RG11, buf, ctx, out)[1]
+
+
+def read_to_bc1(buf, ctx=None, out=None):  # UASTC files only: BC1 of RGB (A dropped)
+    return _read_to(_lib.READ_BC1, buf, ctx, out)[1]
+
+
+def read_to_bc3(buf, ctx=None, out=None):  # UASTC files only: BC3 (BC4 of A, BC1 of RGB)
+    return _read_to(_lib.READ_BC3, buf, ctx, out)[1]
 
 
 def basislz_decode(buf, slice_index=None):

@@ -1210,7 +1210,7 @@ struct BuFilePlan {
 inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t len, BuFilePlan& p, bool check_data_crc = true)
 {
     if (!file) return BU_ERR_ARGUMENT;
-    if ((int)target < 0 || (int)target > (int)BU_READ_EAC_RG11) return BU_ERR_ARGUMENT;
+    if ((int)target < 0 || (int)target > (int)BU_READ_BC3 || (int)target == 10) return BU_ERR_ARGUMENT;  // (10 names no read target)
     bu_status st = read_header(file, len, &p.h);
     if (st) return st;
     if (check_data_crc && crc16(file + 77, len - 77, 0) != p.h.data_crc16) return BU_ERR_DATA_CRC;  // to EOF, basis.rs:338-341
@@ -1219,7 +1219,7 @@ inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t
     if (p.h.tex_format > 1) return BU_ERR_TEX_FORMAT;
     p.etc1s = p.h.tex_format == 0;
     const bool has_alpha = (p.h.flags & 4) != 0;
-    if (p.etc1s && (int)target >= (int)BU_READ_BC4) return BU_ERR_ARGUMENT;  // (ETC1S to the one- and two-channel targets: not offered)
+    if (p.etc1s && (int)target >= (int)BU_READ_BC4) return BU_ERR_ARGUMENT;  // (ETC1S to the channel and colour targets: not offered)
     if (p.etc1s && !(target == BU_READ_RGBA || target == BU_READ_ETC1)) return BU_ERR_UNSUPPORTED;
     if (p.etc1s && has_alpha && (p.slices.size() % 2) != 0) return BU_ERR_ALPHA_SLICES;
     p.alpha_pairs = p.etc1s && has_alpha && target == BU_READ_RGBA;
@@ -1254,7 +1254,8 @@ inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t
             case BU_READ_UASTC: im.size = s.file_size; im.stride = 16u * s.num_blocks_x; break;
             case BU_READ_ETC1:
             case BU_READ_BC4:
-            case BU_READ_EAC_R11: im.size = nb16 * 8; im.stride = 8u * s.num_blocks_x; break;
+            case BU_READ_EAC_R11:
+            case BU_READ_BC1: im.size = nb16 * 8; im.stride = 8u * s.num_blocks_x; break;
             default: im.size = nb16 * 16; im.stride = 16u * s.num_blocks_x; break;
             }
         }

@@ -44,6 +44,8 @@ static bu_target bu_read_block_target(bu_read_target target)
     case BU_READ_BC5: return BU_TARGET_BC5_RG;
     case BU_READ_EAC_R11: return BU_TARGET_EAC_R11;
     case BU_READ_EAC_RG11: return BU_TARGET_EAC_RG11;
+    case BU_READ_BC1: return BU_TARGET_BC1_RGB;
+    case BU_READ_BC3: return BU_TARGET_BC3_RGBA;
     default: return BU_TARGET_ETC2;
     }
 }

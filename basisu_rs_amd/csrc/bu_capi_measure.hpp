@@ -441,7 +441,7 @@ bu_status bu_time_block_api(bu_context* ctx, bu_target target, const uint8_t* bl
 {
     if (!ctx || !blocks || !out || n_blocks == 0 || reps <= 0 || !out_ns_per_call) return BU_ERR_ARGUMENT;
     const size_t bb = bu_target_block_bytes(target);
-    if (bb == 0 || bu_channel_target(target)) return BU_ERR_ARGUMENT;  // (the per-block API has no one- or two-channel member)
+    if (bb == 0 || bu_after_rgba(target)) return BU_ERR_ARGUMENT;  // (the per-block API has no member for the targets encoded after the RGBA32 unpack)
     bu_status st = BU_OK;
     const auto t0 = std::chrono::steady_clock::now();
     for (int r = 0; r < reps && st == BU_OK; r++)

@@ -10,10 +10,12 @@ size_t bu_target_block_bytes(bu_target target)
     case BU_TARGET_BC7:
     case BU_TARGET_ETC2:
     case BU_TARGET_BC5_RG:
-    case BU_TARGET_EAC_RG11: return 16;
+    case BU_TARGET_EAC_RG11:
+    case BU_TARGET_BC3_RGBA: return 16;
     case BU_TARGET_ETC1:
     case BU_TARGET_BC4_R:
-    case BU_TARGET_EAC_R11: return 8;
+    case BU_TARGET_EAC_R11:
+    case BU_TARGET_BC1_RGB: return 8;
     case BU_TARGET_RGBA32: return 64;
     default: return 0;
     }

@@ -112,13 +112,13 @@ unsigned* bu_ticket_for(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: the
 // kernel BU_MULTI_* of target T is bu_multi_kernels[T][BU_MULTI_*]
 static_assert(BU_TARGET_ASTC == BU_TGT_ASTC && BU_TARGET_BC7 == BU_TGT_BC7 && BU_TARGET_ETC1 == BU_TGT_ETC1 && BU_TARGET_ETC2 == BU_TGT_ETC2 &&
               BU_TARGET_RGBA32 == BU_TGT_RGBA && BU_TARGET_BC4_R == BU_TGT_BC4 && BU_TARGET_BC5_RG == BU_TGT_BC5 && BU_TARGET_EAC_R11 == BU_TGT_R11 &&
-                  BU_TARGET_EAC_RG11 == BU_TGT_RG11,
+                  BU_TARGET_EAC_RG11 == BU_TGT_RG11 && BU_TARGET_BC1_RGB == BU_TGT_BC1 && BU_TARGET_BC3_RGBA == BU_TGT_BC3,
               "the launchers index kernels by bu_target");
-constexpr unsigned BU_N_TARGETS = BU_TGT_RG11 + 1;  // (entry 5 of the tables is empty: bu_target 5 names no target, bu_target_block_bytes(5) == 0)
+constexpr unsigned BU_N_TARGETS = BU_TGT_BC3 + 1;  // (entries 5 and 10 of the tables are empty: they name no target, bu_target_block_bytes() == 0)
 using BuPlainFn = decltype(&bu_uastc_kernel<BU_TGT_ASTC>);
 const BuPlainFn bu_plain_kernels[BU_N_TARGETS] = {bu_uastc_kernel<BU_TGT_ASTC>, bu_uastc_kernel<BU_TGT_BC7>, bu_uastc_kernel<BU_TGT_ETC1>, bu_uastc_kernel<BU_TGT_ETC2>,
                                                   bu_uastc_kernel<BU_TGT_RGBA>, nullptr, bu_uastc_kernel<BU_TGT_BC4>, bu_uastc_kernel<BU_TGT_BC5>, bu_uastc_kernel<BU_TGT_R11>,
-                                                  bu_uastc_kernel<BU_TGT_RG11>};
+                                                  bu_uastc_kernel<BU_TGT_RG11>, nullptr, bu_uastc_kernel<BU_TGT_BC1>, bu_uastc_kernel<BU_TGT_BC3>};
 using BuSortedFn = decltype(&bu_uastc_sorted_kernel<BU_TGT_BC7, 1024, 1, 1, false, BU_LAYOUT_STRIP>);
 template <size_t... I>
 constexpr std::array<BuSortedFn, sizeof...(I)> bu_sorted_fns(std::index_sequence<I...>)
@@ -138,7 +138,8 @@ std::array<BuMultiFn, 4> bu_multi_fns()  // indexed by BU_MULTI_*; nullptr where
 }
 const std::array<BuMultiFn, 4> bu_multi_kernels[BU_N_TARGETS] = {bu_multi_fns<BU_TGT_ASTC>(), bu_multi_fns<BU_TGT_BC7>(), bu_multi_fns<BU_TGT_ETC1>(),
                                                                  bu_multi_fns<BU_TGT_ETC2>(), bu_multi_fns<BU_TGT_RGBA>(), {}, bu_multi_fns<BU_TGT_BC4>(),
-                                                                 bu_multi_fns<BU_TGT_BC5>(), bu_multi_fns<BU_TGT_R11>(), bu_multi_fns<BU_TGT_RG11>()};
+                                                                 bu_multi_fns<BU_TGT_BC5>(), bu_multi_fns<BU_TGT_R11>(), bu_multi_fns<BU_TGT_RG11>(), {},
+                                                                 bu_multi_fns<BU_TGT_BC1>(), bu_multi_fns<BU_TGT_BC3>()};
 
 // One slice: resolve the policy, plan (bu_plan_slice), claim tile tickets where the plan asks for them, launch.
 // policy = BU_POLICY_* of this launch, or -1 for the context's (bu_context_set_launch_policy; BU_POLICY_AUTO there is resolved per launch by
@@ -148,7 +149,7 @@ bu_status bu_launch_uastc(bu_context* ctx, bu_target target, const void* d_in, s
                           uint64_t base, uint64_t* d_status, hipStream_t stream, unsigned grid_cap = 0, int policy = BU_POLICY_EXCLUSIVE)
 {
     if (n_blocks == 0) return BU_OK;
-    if (bu_target_block_bytes(target) == 0) return BU_ERR_ARGUMENT;  // (also the empty entry 5 of the kernel tables)
+    if (bu_target_block_bytes(target) == 0) return BU_ERR_ARGUMENT;  // (also the empty entries 5 and 10 of the kernel tables)
     const unsigned cu_count = (unsigned)ctx->cu_count;
     if (policy < 0) policy = ctx->launch_policy.load(std::memory_order_relaxed);
     const bool big = bu_slice_needs_policy(n_blocks, grid_cap, cu_count);

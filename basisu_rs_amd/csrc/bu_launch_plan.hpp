@@ -117,12 +117,13 @@ constexpr BuSortedKey BU_SORTED_KERNELS[] = {
     {BU_TGT_ETC2, 1024, 1, 1, false, false}, {BU_TGT_ETC2, 512, 2, 1, false, false}, {BU_TGT_ETC2, 1024, 4, 1, true, false}, {BU_TGT_ETC2, 1024, 4, 1, true, true},
     {BU_TGT_ETC2, 512, 4, 4, false, false}, {BU_TGT_ETC2, 512, 4, 4, false, true}, {BU_TGT_ETC2, 256, 4, 1, true, false}, {BU_TGT_ETC2, 256, 4, 1, true, true},
     {BU_TGT_RGBA, 1024, 1, 1, true, false}, {BU_TGT_RGBA, 1024, 1, 1, true, true}, {BU_TGT_RGBA, 512, 2, 1, true, false}, {BU_TGT_RGBA, 512, 2, 1, true, true},
-// the one- and two-channel targets: the ETC shapes they are planned in (bu_shape_target) -- one tile per CU, the mid shape, the exclusive and the
-// shared large shapes (strips and rectangles), the zero-copy shape
+// the targets encoded after the RGBA32 unpack (one- and two-channel, then colour): the ETC shapes they are planned in (bu_shape_target) -- one
+// tile per CU, the mid shape, the exclusive and the shared large shapes (strips and rectangles), the zero-copy shape
 #define BU_CHANNEL_SHAPES(T, SHARED_PREFETCH)                                                                                                   \
     {T, 1024, 1, 1, false, false}, {T, 512, 2, 1, false, false}, {T, 1024, 4, 1, true, false}, {T, 1024, 4, 1, true, true},                     \
     {T, 512, 4, 4, SHARED_PREFETCH, false}, {T, 512, 4, 4, SHARED_PREFETCH, true}, {T, 256, 4, 1, true, false}
     BU_CHANNEL_SHAPES(BU_TGT_BC4, true), BU_CHANNEL_SHAPES(BU_TGT_BC5, false), BU_CHANNEL_SHAPES(BU_TGT_R11, true), BU_CHANNEL_SHAPES(BU_TGT_RG11, false),
+    BU_CHANNEL_SHAPES(BU_TGT_BC1, true), BU_CHANNEL_SHAPES(BU_TGT_BC3, false),
 #undef BU_CHANNEL_SHAPES
 };
 constexpr int bu_sorted_kernel(int target, const BuShape& s, bool rect)

@@ -171,7 +171,8 @@ struct BuTablesAll {  // the device blob: one allocation, one kernel argument
 static_assert(offsetof(BuTablesAll, t) == sizeof(BuBc7Tables), "bu_bc7_tables() steps back by sizeof(BuBc7Tables)");
 
 // byte ranges [lo, hi) of BuTables a target reads (target ids as in bu_uastc_dispatch.hpp: 0 ASTC, 1 BC7, 2 ETC1, 3 ETC2,
-// 4 RGBA32); a second range is empty unless lo2 < hi2.  All bounds are multiples of 16.
+// 4 RGBA32, 6..9 the channel targets, 11 / 12 BC1 / BC3, which read what RGBA32 reads); a second range is empty unless lo2 < hi2.
+// All bounds are multiples of 16.
 struct BuTableRange {
     unsigned lo, hi, lo2, hi2;
 };
@@ -179,7 +180,7 @@ constexpr BuTableRange bu_table_range(int target)
 {
     return target == 1   ? BuTableRange{(unsigned)offsetof(BuTables, trit5), (unsigned)offsetof(BuTables, part), 0u, 0u}
            : target == 0 ? BuTableRange{(unsigned)offsetof(BuTables, trit5), (unsigned)offsetof(BuTables, etc1_mod), 0u, 0u}
-           : target == 4 ? BuTableRange{(unsigned)offsetof(BuTables, trit5), (unsigned)offsetof(BuTables, w3mask_u), 0u, 0u}
+           : (target == 4 || target == 11 || target == 12) ? BuTableRange{(unsigned)offsetof(BuTables, trit5), (unsigned)offsetof(BuTables, w3mask_u), 0u, 0u}
                          : BuTableRange{(unsigned)offsetof(BuTables, trit5), (unsigned)offsetof(BuTables, w3mask_u),
                                         (unsigned)offsetof(BuTables, etc1_mod), (unsigned)offsetof(BuTables, end_marker)};
 }

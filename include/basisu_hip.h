@@ -46,7 +46,14 @@ typedef enum bu_target {
     BU_TARGET_BC4_R = 6,    /*  8 B/block  BC4 UNORM of R                        */
     BU_TARGET_BC5_RG = 7,   /* 16 B/block  BC5 UNORM: X = R, Y = A               */
     BU_TARGET_EAC_R11 = 8,  /*  8 B/block  ETC2 EAC R11 unsigned of R            */
-    BU_TARGET_EAC_RG11 = 9  /* 16 B/block  ETC2 EAC RG11 unsigned: X = R, Y = A  */
+    BU_TARGET_EAC_RG11 = 9, /* 16 B/block  ETC2 EAC RG11 unsigned: X = R, Y = A  */
+    /* Colour targets (no counterpart in the reference; an exact integer encoder).  Their input is what
+     * BU_TARGET_RGBA32 writes for the block.  BC1 encodes R, G, B in four-colour mode and drops A; BC3 is BC4 of A (section 4.4)
+     * followed by that BC1 block.  The slice, batch and in-flight entry points take them with the semantics of BU_TARGET_ETC1
+     * (BC1) / BU_TARGET_ETC2 (BC3); the bu_transcode_uastc_block_to_* family does not. */
+    /* (10 names no target, as 5 does -- bu_target_block_bytes(10) == 0) */
+    BU_TARGET_BC1_RGB = 11,  /*  8 B/block  BC1 UNORM, opaque RGB             */
+    BU_TARGET_BC3_RGBA = 12  /* 16 B/block  BC3 UNORM: BC4 of A, then BC1 of RGB */
 } bu_target;
 
 typedef enum bu_status {
@@ -84,7 +91,8 @@ void bu_context_destroy(bu_context* ctx);
 const char* bu_status_string(bu_status st);
 /* detail of the last BU_ERR_HIP on this context (never NULL) */
 const char* bu_last_error(const bu_context* ctx);
-/* bytes per output block: 16, 16, 8, 16, 64 (uastc.rs:13-17), 0 for 5, then 8, 16, 8, 16 (BC4, BC5, EAC R11, EAC RG11: 6..9); 0 for an unknown target */
+/* bytes per output block: 16, 16, 8, 16, 64 (uastc.rs:13-17), 0 for 5, then 8, 16, 8, 16 (BC4, BC5, EAC R11, EAC RG11: 6..9), 0 for 10,
+ * then 8, 16 (BC1, BC3: 11, 12); 0 for an unknown target */
 size_t bu_target_block_bytes(bu_target target);
 
 /* ---- launch policy -------------------------------------------------------------------------------
@@ -337,7 +345,10 @@ typedef enum bu_read_target {
     BU_READ_BC4 = 6,
     BU_READ_BC5 = 7,
     BU_READ_EAC_R11 = 8,
-    BU_READ_EAC_RG11 = 9
+    BU_READ_EAC_RG11 = 9,
+    /* UASTC files only (BU_TARGET_BC1_RGB / BU_TARGET_BC3_RGBA per slice); an ETC1S file returns BU_ERR_ARGUMENT; 10 names no read target */
+    BU_READ_BC1 = 11,
+    BU_READ_BC3 = 12
 } bu_read_target;
 
 /* read_header (basis.rs:307-336): signature, size, header_size == 77, header CRC */
@@ -349,7 +360,7 @@ bu_status bu_basis_read_slice_descs(const uint8_t* file, size_t len, const bu_ba
 uint16_t bu_basis_crc16(const uint8_t* data, size_t len, uint16_t crc);
 /* number of images and output bytes bu_read_to() will produce for this file (no GPU work) */
 bu_status bu_read_query(bu_read_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes);
-/* read_to_{rgba,etc1,etc2,uastc,astc,bc7} (and bc4, bc5, eac_r11, eac_rg11 for UASTC files): every slice of the file (every colour/alpha pair for RGBA from an
+/* read_to_{rgba,etc1,etc2,uastc,astc,bc7} (and bc4, bc5, eac_r11, eac_rg11, bc1, bc3 for UASTC files): every slice of the file (every colour/alpha pair for RGBA from an
  * ETC1S file with alpha) becomes one bu_image whose bytes are written to `out`.  header_out may be NULL.
  * Reference quirks are reproduced: the data CRC covers bytes[77..EOF]; total_selectors sizes BOTH ETC1S
  * codebooks (basis.rs:289-291); ETC1S RGBA images report stride 16*orig_width (basis.rs:46,64).
@@ -503,7 +514,7 @@ bu_status bu_time_etc1s_launches_streams_window(bu_context* ctx, int rgba, const
                                                 float* out_event_ms, float* out_host_ms);
 /* The reference's micro-benchmark shape (benches/benchmark.rs:66-98): `reps` passes over `n_blocks` blocks, one per-block API
  * call per block (RGBA32: bu_unpack_uastc_block_to_rgba), host steady clock around the loop; nanoseconds per call.
- * The one- and two-channel targets have no per-block function: BU_ERR_ARGUMENT. */
+ * The one- and two-channel targets and the colour targets have no per-block function: BU_ERR_ARGUMENT. */
 bu_status bu_time_block_api(bu_context* ctx, bu_target target, const uint8_t* blocks, size_t n_blocks, int reps, uint8_t* out,
                             float* out_ns_per_call);
 bu_status bu_time_copy_launches(bu_context* ctx, const void* const* d_in, void* const* d_out, size_t n_buffers,

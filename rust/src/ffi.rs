@@ -22,6 +22,8 @@ pub const BU_TARGET_BC4_R: c_int = 6;
 pub const BU_TARGET_BC5_RG: c_int = 7;
 pub const BU_TARGET_EAC_R11: c_int = 8;
 pub const BU_TARGET_EAC_RG11: c_int = 9;
+pub const BU_TARGET_BC1_RGB: c_int = 11;
+pub const BU_TARGET_BC3_RGBA: c_int = 12;
 // bu_read_target
 pub const BU_READ_RGBA: c_int = 0;
 pub const BU_READ_ETC1: c_int = 1;
@@ -33,6 +35,8 @@ pub const BU_READ_BC4: c_int = 6;
 pub const BU_READ_BC5: c_int = 7;
 pub const BU_READ_EAC_R11: c_int = 8;
 pub const BU_READ_EAC_RG11: c_int = 9;
+pub const BU_READ_BC1: c_int = 11;
+pub const BU_READ_BC3: c_int = 12;
 pub const BU_OK: c_int = 0;
 pub const BU_COMM_ID_BYTES: usize = 128;
 pub const BU_IPC_HANDLE_BYTES: usize = 64;

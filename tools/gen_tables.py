@@ -119,6 +119,15 @@ def brute_mode5():
     return tab
 
 
+def bc1_solid_pairs(bits):
+    """for every 8-bit v, the (a, b) of `bits`-bit values whose thirds point 2 e(a) + e(b) lies nearest 3v
+    (e = bit replication to 8 bits); ties -> smaller |a - b|, then smaller a, then smaller b.  Exhaustive."""
+    n = 1 << bits
+    e = [(c << (8 - bits)) | (c >> (2 * bits - 8)) for c in range(n)]
+    return [min(((a, b) for a in range(n) for b in range(n)), key=lambda p: (abs(2 * e[p[0]] + e[p[1]] - 3 * v), abs(p[0] - p[1]), p[0], p[1]))
+            for v in range(256)]
+
+
 def fmt_array(ctype, name, vals, per_line=12, hexw=None):
     lines = []
     for i in range(0, len(vals), per_line):
@@ -303,6 +312,13 @@ def main():
     out.append(fmt_array("int8_t", "BU_ETC2_ALPHA_MOD", am, 8))
     out.append("// selector id -> ETC1 2-bit code (etc.rs:433)\n")
     out.append(fmt_array("uint8_t", "BU_SEL_TO_ETC1", ints(table_body(etc, "SELECTOR_ID_TO_ETC1")), 4))
+
+    # ---- BC1 solid-colour endpoints (no counterpart in the reference) ----
+    out.append("// BC1 solid colour, 5-bit channel: v -> a | b<<8, the pair minimising |2 e5(a) + e5(b) - 3v|, then |a - b|, then a, then b\n"
+               "// (exhaustive search, bc1_solid_pairs)\n")
+    out.append(fmt_array("uint16_t", "BU_BC1_OM5", [a | (b << 8) for a, b in bc1_solid_pairs(5)], 12, 4))
+    out.append("// the same for the 6-bit channel (e6)\n")
+    out.append(fmt_array("uint16_t", "BU_BC1_OM6", [a | (b << 8) for a, b in bc1_solid_pairs(6)], 12, 4))
 
 
     # ======================= oracle tables (unpacked, formula-level) =======================
