@@ -206,6 +206,34 @@ class Context:
         self._check(st, bad)
         return out[: n * 64]
 
+    def etc1s_transcode(self, target, idx, alpha_idx, endpoints, selectors):
+        """ETC1S slice -> BC1, BC3, BC4, BC5, EAC R11 or EAC RG11 (target: a TargetTextureFormat of the six), one block per index;
+        alpha_idx (or None) is the paired alpha slice, A = 255 without one.  Returns bytes [n_blocks * block bytes]."""
+        t = int(target)
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        aptr = None
+        if alpha_idx is not None:
+            alpha_idx = np.ascontiguousarray(alpha_idx, dtype=np.uint32)
+            if alpha_idx.size != idx.size:
+                raise ValueError("alpha_idx must hold one entry per block")
+            aptr = alpha_idx.ctypes.data
+        endpoints = np.ascontiguousarray(endpoints, dtype=np.uint32)
+        selectors = np.ascontiguousarray(selectors, dtype=np.uint8).reshape(-1, 8)
+        out = np.empty(max(idx.size, 1) * max(_lib.BLOCK_BYTES.get(t, 0), 1), dtype=np.uint8)
+        bad = ctypes.c_uint64(0)
+        st = self._lib.bu_etc1s_transcode(self._h, t, idx.ctypes.data, aptr, idx.size, endpoints.ctypes.data, endpoints.size,
+                                          selectors.ctypes.data, selectors.shape[0], out.ctypes.data, out.size, ctypes.byref(bad))
+        self._check(st, bad)
+        return out[: idx.size * _lib.BLOCK_BYTES[t]]
+
+    def etc1s_transcode_device(self, target, d_idx, d_alpha_idx, n_blocks, d_endpoints, n_endpoints, d_selectors, n_selectors, d_out,
+                               d_status=None, stream=None):
+        """the device form of etc1s_transcode (torch tensors or raw pointers); enqueues only"""
+        st = self._lib.bu_etc1s_transcode_device(self._h, int(target), _ptr(d_idx), _ptr(d_alpha_idx), int(n_blocks), _ptr(d_endpoints),
+                                                 int(n_endpoints), _ptr(d_selectors), int(n_selectors), _ptr(d_out), _ptr(d_status),
+                                                 _stream_ptr(stream))
+        self._check(st)
+
     # ---- device-pointer API (torch tensors or raw pointers) ---------------------------------------
     def transcode_device(self, fmt, d_in, n_blocks, d_out, blocks_per_row=0, block_index_base=0, d_status=None, stream=None):
         st = self._lib.bu_uastc_transcode_device(self._h, int(fmt), _ptr(d_in), int(n_blocks), _ptr(d_out), int(blocks_per_row),

@@ -554,12 +554,22 @@ void bu_etc1s_selector_from_rows(const uint8_t rows[4], uint8_t out_entry[8]) { 
 // reports (bu_context_create: etc1s_lds_limit); if that fails too the L2-gather kernels serve every size.  The granted size is
 // remembered per kernel in an atomic (the device entry points may be called from several threads; asking twice is harmless):
 // 0 = not asked yet, 1 = refused, otherwise the bytes allowed.
-static bool bu_etc1s_staged_ok(bu_context* ctx, bool rgba, size_t lds)
+// Kernel k of the LDS-staged ETC1S kernels: 0 ETC1, 1 RGBA32, 2.. the targets of bu_etc1s_transcode_device (bu_etc1s_target_slot).
+static const void* bu_etc1s_staged_fn(unsigned k)
 {
-    std::atomic<size_t>& state = ctx->etc1s_lds_state[rgba ? 1 : 0];
+    static const void* const fns[8] = {
+        reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<false>), reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<true>),
+        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC4, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC5, true>),
+        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_R11, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_RG11, true>),
+        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC1, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC3, true>)};
+    return fns[k];
+}
+static bool bu_etc1s_staged_ok(bu_context* ctx, unsigned k, size_t lds)
+{
+    std::atomic<size_t>& state = ctx->etc1s_lds_state[k];
     size_t s = state.load(std::memory_order_acquire);
     if (s == 0) {
-        const void* fn = rgba ? reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<true>) : reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<false>);
+        const void* fn = bu_etc1s_staged_fn(k);
         s = 1;
         for (const size_t want : {(size_t)BU_ETC1S_LDS_MAX, ctx->etc1s_lds_limit}) {
             if (want < 4096 || want > BU_ETC1S_LDS_MAX) continue;
@@ -581,7 +591,7 @@ bu_status bu_etc1s_transcode_etc1_device(bu_context* ctx, const uint32_t* d_idx,
     if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
     if (n_blocks == 0) return BU_OK;
     const size_t lds = ((size_t)n_endpoints + n_selectors) * 4;
-    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, false, lds)) {
+    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, 0, lds)) {
         // codebooks in LDS, one persistent workgroup per CU (with four blocks per lane and step in flight a second workgroup only
         // doubles the staging: 2^21 blocks 8.0 against 9.3 us, 2^22 12.95 / 13.2, 2^24 37.4 / 39.3)
         const unsigned per_cu = 1u;
@@ -606,7 +616,7 @@ bu_status bu_etc1s_decode_rgba_device(bu_context* ctx, const uint32_t* d_idx, co
     if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
     if (n_blocks == 0) return BU_OK;
     const size_t lds = ((size_t)n_endpoints + n_selectors + 256) * 4;
-    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, true, lds)) {
+    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, 1, lds)) {
         hipLaunchKernelGGL(bu_etc1s_staged_kernel<true>, dim3((unsigned)ctx->cu_count), dim3(1024), lds, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx,
                            (unsigned)nbx, n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors,
                            static_cast<uint8_t*>(d_out), reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
@@ -620,13 +630,58 @@ bu_status bu_etc1s_decode_rgba_device(bu_context* ctx, const uint32_t* d_idx, co
     return BU_OK;
 }
 
-static bu_status bu_etc1s_host(bu_context* ctx, bool rgba, const uint32_t* idx, const uint32_t* alpha_idx, size_t nbx, size_t nby,
+// the slot of an ETC1S target in bu_etc1s_staged_fn / etc1s_lds_state (2..7), or 0 for a target bu_etc1s_transcode_device refuses
+static unsigned bu_etc1s_target_slot(bu_target target)
+{
+    switch (target) {
+    case BU_TARGET_BC4_R: return 2;
+    case BU_TARGET_BC5_RG: return 3;
+    case BU_TARGET_EAC_R11: return 4;
+    case BU_TARGET_EAC_RG11: return 5;
+    case BU_TARGET_BC1_RGB: return 6;
+    case BU_TARGET_BC3_RGBA: return 7;
+    default: return 0;
+    }
+}
+
+bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uint32_t* d_idx, const uint32_t* d_alpha_idx, size_t n_blocks,
+                                    const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors,
+                                    void* d_out, uint64_t* d_status, void* stream)
+{
+    const unsigned k = bu_etc1s_target_slot(target);
+    if (!ctx || k == 0 || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(d_out) % bu_target_block_bytes(target)) return BU_ERR_ARGUMENT;
+    if (n_blocks == 0) return BU_OK;
+    typedef void (*Fn)(const uint32_t*, const uint32_t*, size_t, const uint32_t*, uint32_t, const uint2*, uint32_t, void*, unsigned long long*,
+                       const BuTablesAll*);
+    static const Fn gather[8] = {nullptr, nullptr, &bu_etc1s_target_kernel<BU_TGT_BC4, false>, &bu_etc1s_target_kernel<BU_TGT_BC5, false>,
+                                 &bu_etc1s_target_kernel<BU_TGT_R11, false>, &bu_etc1s_target_kernel<BU_TGT_RG11, false>,
+                                 &bu_etc1s_target_kernel<BU_TGT_BC1, false>, &bu_etc1s_target_kernel<BU_TGT_BC3, false>};
+    static const Fn staged_fn[8] = {nullptr, nullptr, &bu_etc1s_target_kernel<BU_TGT_BC4, true>, &bu_etc1s_target_kernel<BU_TGT_BC5, true>,
+                                    &bu_etc1s_target_kernel<BU_TGT_R11, true>, &bu_etc1s_target_kernel<BU_TGT_RG11, true>,
+                                    &bu_etc1s_target_kernel<BU_TGT_BC1, true>, &bu_etc1s_target_kernel<BU_TGT_BC3, true>};
+    // both codebooks and the palette table in LDS from BU_ETC1S_STAGED_MIN blocks (the rule of the ETC1 and RGBA32 calls), one
+    // persistent workgroup per CU
+    const size_t lds = ((size_t)n_endpoints + n_selectors + 256) * 4;
+    const bool staged = n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, k, lds);
+    hipLaunchKernelGGL(staged ? staged_fn[k] : gather[k],
+                       dim3(staged ? (unsigned)ctx->cu_count : bu_grid_for(n_blocks, ctx->cu_count)), dim3(staged ? 1024 : BU_WG),
+                       staged ? lds : 0, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx, n_blocks, d_endpoints, n_endpoints,
+                       static_cast<const uint2*>(d_selectors), n_selectors, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    BU_HIP(ctx, hipGetLastError());
+    return BU_OK;
+}
+
+// The host-pointer ETC1S calls: stage the indices and both codebooks, launch `target`'s device call (BU_TARGET_ETC1,
+// BU_TARGET_RGBA32 -- nbx x nby blocks -- or one of bu_etc1s_transcode_device's), copy back and synchronise.
+static bu_status bu_etc1s_host(bu_context* ctx, bu_target target, const uint32_t* idx, const uint32_t* alpha_idx, size_t nbx, size_t nby,
                                const uint32_t* endpoints, uint32_t n_ep, const uint8_t* selectors, uint32_t n_sel, uint8_t* out,
                                size_t out_bytes, uint64_t* first_bad)
 {
+    const bool rgba = target == BU_TARGET_RGBA32;
     const size_t n = nbx * nby;
     if (!ctx || !out || (n && (!idx || !endpoints || !selectors))) return BU_ERR_ARGUMENT;
-    const size_t bb = rgba ? 64 : 8;
+    const size_t bb = bu_target_block_bytes(target);
     if (out_bytes < n * bb) return BU_ERR_OUTPUT_SIZE;
     if (n == 0) return BU_OK;
     std::lock_guard<std::mutex> g(ctx->lock);
@@ -650,12 +705,15 @@ static bu_status bu_etc1s_host(bu_context* ctx, bool rgba, const uint32_t* idx, 
     uint64_t* ds = reinterpret_cast<uint64_t*>(ctx->d_status);
     const uint32_t* d_ep = reinterpret_cast<const uint32_t*>(aux);
     const void* d_sel = aux + ep_bytes;
+    const uint32_t* d_aidx = alpha_idx ? reinterpret_cast<const uint32_t*>(aux + ep_bytes + sel_bytes) : nullptr;
     if (rgba)
-        st = bu_etc1s_decode_rgba_device(ctx, static_cast<const uint32_t*>(ctx->d_in),
-                                         alpha_idx ? reinterpret_cast<const uint32_t*>(aux + ep_bytes + sel_bytes) : nullptr, nbx, nby, d_ep,
-                                         n_ep, d_sel, n_sel, ctx->d_out, ds, ctx->stream);
-    else
+        st = bu_etc1s_decode_rgba_device(ctx, static_cast<const uint32_t*>(ctx->d_in), d_aidx, nbx, nby, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds,
+                                         ctx->stream);
+    else if (target == BU_TARGET_ETC1)
         st = bu_etc1s_transcode_etc1_device(ctx, static_cast<const uint32_t*>(ctx->d_in), n, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds, ctx->stream);
+    else
+        st = bu_etc1s_transcode_device(ctx, target, static_cast<const uint32_t*>(ctx->d_in), d_aidx, n, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds,
+                                       ctx->stream);
     if (st) return st;
     BU_HIP(ctx, hipMemcpyAsync(&word, ctx->d_status, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
     BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, n * bb, hipMemcpyDeviceToHost, ctx->stream));
@@ -667,7 +725,7 @@ static bu_status bu_etc1s_host(bu_context* ctx, bool rgba, const uint32_t* idx, 
 bu_status bu_etc1s_transcode_etc1(bu_context* ctx, const uint32_t* idx, size_t n_blocks, const uint32_t* endpoints, uint32_t n_endpoints,
                                   const uint8_t* selectors, uint32_t n_selectors, uint8_t* out, size_t out_bytes, uint64_t* first_bad_block)
 {
-    return bu_etc1s_host(ctx, false, idx, nullptr, n_blocks, 1, endpoints, n_endpoints, selectors, n_selectors, out, out_bytes, first_bad_block);
+    return bu_etc1s_host(ctx, BU_TARGET_ETC1, idx, nullptr, n_blocks, 1, endpoints, n_endpoints, selectors, n_selectors, out, out_bytes, first_bad_block);
 }
 
 bu_status bu_etc1s_decode_rgba(bu_context* ctx, const uint32_t* idx, const uint32_t* alpha_idx, size_t nbx, size_t nby,
@@ -675,7 +733,15 @@ bu_status bu_etc1s_decode_rgba(bu_context* ctx, const uint32_t* idx, const uint3
                                size_t out_bytes, uint64_t* first_bad_block)
 {
     if (nbx == 0 && nby != 0) return BU_ERR_ARGUMENT;
-    return bu_etc1s_host(ctx, true, idx, alpha_idx, nbx, nby, endpoints, n_endpoints, selectors, n_selectors, out, out_bytes, first_bad_block);
+    return bu_etc1s_host(ctx, BU_TARGET_RGBA32, idx, alpha_idx, nbx, nby, endpoints, n_endpoints, selectors, n_selectors, out, out_bytes, first_bad_block);
+}
+
+bu_status bu_etc1s_transcode(bu_context* ctx, bu_target target, const uint32_t* idx, const uint32_t* alpha_idx, size_t n_blocks,
+                             const uint32_t* endpoints, uint32_t n_endpoints, const uint8_t* selectors, uint32_t n_selectors, uint8_t* out,
+                             size_t out_bytes, uint64_t* first_bad_block)
+{
+    if (bu_etc1s_target_slot(target) == 0) return BU_ERR_ARGUMENT;
+    return bu_etc1s_host(ctx, target, idx, alpha_idx, n_blocks, 1, endpoints, n_endpoints, selectors, n_selectors, out, out_bytes, first_bad_block);
 }
 
 

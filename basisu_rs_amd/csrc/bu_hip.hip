@@ -34,6 +34,7 @@
 #include "bu_basis.hpp"
 #include "bu_batch_plan.hpp"   // slices -> runs -> launches of the batch entry points (host only)
 #include "bu_uastc_dispatch.hpp"
+#include "bu_etc1s_targets.hpp"   // ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 per block (palette form)
 #include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 
 #include "bu_kernels.hpp"        // device code

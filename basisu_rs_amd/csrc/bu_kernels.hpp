@@ -915,6 +915,68 @@ __global__ __launch_bounds__(1024) void bu_etc1s_staged_kernel(const uint32_t* _
 // blocks from which the staged kernel is launched, and the LDS one CU can give a workgroup (160 KiB less a margin)
 constexpr size_t BU_ETC1S_STAGED_MIN = (size_t)1 << 19, BU_ETC1S_LDS_MAX = 152 * 1024;
 
+// ---- ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / EAC RG11 (bu_etc1s_targets.hpp) ---------------------------
+// One lane per block and step, grid-stride, the next step's indices in flight.  STAGED = false: the L2 gather of the kernels above,
+// 256-thread workgroups, the palette table in LDS.  STAGED = true: one persistent 1024-thread workgroup per CU with both codebooks
+// (endpoint words, selector rows) and the palette table in dynamic LDS, as bu_etc1s_staged_kernel<true> lays them out.  A wave's 64
+// lanes hold 64 consecutive blocks, so each result store instruction writes 512 B (8-byte targets) or 1 KiB contiguous: whole cache
+// lines for an output aligned to them.  Index errors report as the RGBA32 kernels do and leave a zero block.
+template <int TARGET, bool STAGED>
+__global__ __launch_bounds__(STAGED ? 1024 : BU_WG) void bu_etc1s_target_kernel(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ aidx,
+                                                                                size_t n_blocks, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
+                                                                                const uint2* __restrict__ selectors, uint32_t n_sel,
+                                                                                void* __restrict__ out, unsigned long long* status,
+                                                                                const BuTablesAll* __restrict__ tables)
+{
+    constexpr unsigned WGS = STAGED ? 1024u : (unsigned)BU_WG;
+    extern __shared__ uint32_t bu_etc1s_tgt_lds[];
+    __shared__ uint32_t s_pal_static[STAGED ? 1 : 256];
+    uint32_t* s_ep = bu_etc1s_tgt_lds;
+    uint32_t* s_sel = bu_etc1s_tgt_lds + n_ep;
+    uint32_t* pal = STAGED ? s_sel + n_sel : s_pal_static;
+    const size_t stride = (size_t)gridDim.x * WGS, first = (size_t)blockIdx.x * WGS + threadIdx.x;
+    uint32_t cur = 0, acur = 0;
+    if (first < n_blocks) {
+        cur = __builtin_nontemporal_load(idx + first);
+        if (aidx) acur = __builtin_nontemporal_load(aidx + first);
+    }
+    if constexpr (STAGED) {
+        for (uint32_t i = threadIdx.x; i < n_ep; i += WGS) s_ep[i] = endpoints[i];
+        for (uint32_t i = threadIdx.x; i < n_sel; i += WGS) s_sel[i] = selectors[i].x;
+    }
+    if (threadIdx.x < 256) pal[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
+    __syncthreads();
+    const BuTables& T = tables->t;  // (R11 / RG11: the EAC tables, read through the scalar cache in the table search)
+    for (size_t i = first; i < n_blocks; i += stride) {
+        const size_t in = i + stride;
+        uint32_t nxt = 0, anxt = 0;
+        if (in < n_blocks) {
+            nxt = __builtin_nontemporal_load(idx + in);
+            if (aidx) anxt = __builtin_nontemporal_load(aidx + in);
+        }
+        const uint32_t e = cur & 0xFFFFu, sl = cur >> 16, ae = acur & 0xFFFFu, as = acur >> 16;
+        const bool bad = e >= n_ep || sl >= n_sel || (aidx && (ae >= n_ep || as >= n_sel));
+        uint32_t o[4] = {0, 0, 0, 0};
+        if (bad) {
+            bu_report(status, i, BU_ERR_INDEX_RANGE);
+        } else {
+            const uint32_t ep = STAGED ? s_ep[e] : endpoints[e], rows = STAGED ? s_sel[sl] : selectors[sl].x;
+            uint32_t aep = 0, arows = 0;
+            if (aidx) {
+                aep = STAGED ? s_ep[ae] : endpoints[ae];
+                arows = STAGED ? s_sel[as] : selectors[as].x;
+            }
+            uint32_t pr, pg, pb, pa;
+            bu_etc1s_palettes(pal, ep, aep, pr, pg, pb, pa);
+            bu_etc1s_target_block<TARGET>(T, pr, pg, pb, rows, aidx != nullptr, pa, arows, o);
+        }
+        if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out) + i, make_uint2(o[0], o[1]));
+        else bu_st_stream(reinterpret_cast<uint4*>(out) + i, make_uint4(o[0], o[1], o[2], o[3]));
+        cur = nxt;
+        acur = anxt;
+    }
+}
+
 // ---- whole-file ETC1S launches (bu_read_to): every slice of the file in ONE launch -----------------------------------
 // The host concatenates the per-slice index arrays (each padded to a multiple of 64 words) and describes the slices in a
 // small table; a wave owns one 64-block unit, finds its slice by a scalar binary search over the units' prefix and then

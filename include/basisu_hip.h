@@ -297,6 +297,21 @@ bu_status bu_etc1s_transcode_etc1(bu_context* ctx, const uint32_t* idx, size_t n
 bu_status bu_etc1s_decode_rgba(bu_context* ctx, const uint32_t* idx, const uint32_t* alpha_idx, size_t nbx, size_t nby,
                                const uint32_t* endpoints, uint32_t n_endpoints, const uint8_t* selectors,
                                uint32_t n_selectors, uint8_t* out, size_t out_bytes, uint64_t* first_bad_block);
+/* ETC1S -> BU_TARGET_BC1_RGB, BU_TARGET_BC3_RGBA, BU_TARGET_BC4_R, BU_TARGET_BC5_RG, BU_TARGET_EAC_R11 or BU_TARGET_EAC_RG11
+ * (DESIGN.md section 4.6); any other target, ETC1 and RGBA32 included, returns BU_ERR_ARGUMENT.  Block-linear output,
+ * bu_target_block_bytes(target) bytes per block: block i is the target's rule (sections 4.4 / 4.5) applied to block i of what
+ * bu_etc1s_decode_rgba_device writes for the same indices and codebooks -- RGB from the colour endpoint and selector, A = the alpha
+ * endpoint's green at the alpha selector, or 255 when d_alpha_idx is NULL; the two-channel targets take X = R and Y = A.
+ * Status as that call: BU_ERR_INDEX_RANGE at the lowest block whose colour or alpha index is outside a codebook (an alpha
+ * index array is validated whether the target reads A or not; the block is written as zeros).  d_out must be aligned to the
+ * block size (else BU_ERR_ARGUMENT); n_blocks == 0 returns BU_OK; d_status may be NULL.  The device form never synchronises or
+ * allocates and may be captured in a graph; from 2^19 blocks the codebooks are staged in LDS when they fit. */
+bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uint32_t* d_idx, const uint32_t* d_alpha_idx,
+                                    size_t n_blocks, const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors,
+                                    uint32_t n_selectors, void* d_out, uint64_t* d_status, void* stream);
+bu_status bu_etc1s_transcode(bu_context* ctx, bu_target target, const uint32_t* idx, const uint32_t* alpha_idx, size_t n_blocks,
+                             const uint32_t* endpoints, uint32_t n_endpoints, const uint8_t* selectors, uint32_t n_selectors,
+                             uint8_t* out, size_t out_bytes, uint64_t* first_bad_block);
 
 /* ---- whole-file level: the crate's public read_to_* API (src/lib.rs:20-22, src/basis.rs) -------------
  * Host side in C++ (container parse, CRC-16, BasisLZ entropy decode -- byte/symbol serial, stays on the CPU),
@@ -341,12 +356,14 @@ typedef enum bu_read_target {
     BU_READ_UASTC = 3, /* read_to_uastc basis.rs:175 */
     BU_READ_ASTC = 4, /* read_to_astc  basis.rs:204 */
     BU_READ_BC7 = 5,  /* read_to_bc7   basis.rs:233 */
-    /* UASTC files only (BU_TARGET_BC4_R .. BU_TARGET_EAC_RG11 per slice); an ETC1S file returns BU_ERR_ARGUMENT */
+    /* UASTC files only (BU_TARGET_BC4_R .. BU_TARGET_EAC_RG11 per slice); an ETC1S file returns BU_ERR_ARGUMENT -- its slices take
+     * bu_basislz_decode, then bu_etc1s_transcode */
     BU_READ_BC4 = 6,
     BU_READ_BC5 = 7,
     BU_READ_EAC_R11 = 8,
     BU_READ_EAC_RG11 = 9,
-    /* UASTC files only (BU_TARGET_BC1_RGB / BU_TARGET_BC3_RGBA per slice); an ETC1S file returns BU_ERR_ARGUMENT; 10 names no read target */
+    /* UASTC files only (BU_TARGET_BC1_RGB / BU_TARGET_BC3_RGBA per slice); an ETC1S file returns BU_ERR_ARGUMENT (its slices: bu_basislz_decode,
+     * then bu_etc1s_transcode); 10 names no read target */
     BU_READ_BC1 = 11,
     BU_READ_BC3 = 12
 } bu_read_target;

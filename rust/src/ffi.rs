@@ -155,6 +155,13 @@ extern "C" {
     pub fn bu_etc1s_decode_rgba(ctx: *mut bu_context, idx: *const u32, alpha_idx: *const u32, nbx: usize, nby: usize,
                                 endpoints: *const u32, n_endpoints: u32, selectors: *const u8, n_selectors: u32, out: *mut u8,
                                 out_bytes: usize, first_bad_block: *mut u64) -> c_int;
+    // ETC1S -> BC1, BC3, BC4, BC5, EAC R11, EAC RG11 (target: BU_TARGET_*; any other returns BU_ERR_ARGUMENT); alpha_idx may be null
+    pub fn bu_etc1s_transcode_device(ctx: *mut bu_context, target: c_int, d_idx: *const u32, d_alpha_idx: *const u32, n_blocks: usize,
+                                     d_endpoints: *const u32, n_endpoints: u32, d_selectors: *const c_void, n_selectors: u32,
+                                     d_out: *mut c_void, d_status: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn bu_etc1s_transcode(ctx: *mut bu_context, target: c_int, idx: *const u32, alpha_idx: *const u32, n_blocks: usize,
+                              endpoints: *const u32, n_endpoints: u32, selectors: *const u8, n_selectors: u32, out: *mut u8,
+                              out_bytes: usize, first_bad_block: *mut u64) -> c_int;
     // whole-file level (basis.rs)
     pub fn bu_basis_read_header(file: *const u8, len: usize, out: *mut bu_basis_header) -> c_int;
     pub fn bu_basis_read_slice_descs(file: *const u8, len: usize, header: *const bu_basis_header, out: *mut bu_slice_desc,
