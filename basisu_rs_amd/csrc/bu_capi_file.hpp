@@ -85,6 +85,14 @@ static bu_status bu_basislz_decode_impl(const uint8_t* file, size_t len, uint32_
     return st;
 }
 
+// The whole-file ETC1S kernel (bu_etc1s_kernels.hpp) over the 64-block units [u0, u1) of the slices d_descs describes, on the context
+// stream: RGBA32 or ETC1, both codebooks of n_cb entries.  The caller asks hipGetLastError.
+static void bu_etc1s_file_launch(bu_context* ctx, bool rgba, unsigned grid, const uint32_t* d_idx, const BuEtc1sSlice* d_descs, uint32_t n_slices,
+                                 uint32_t u0, uint32_t u1, const uint32_t* d_ep, const uint2* d_sel, uint32_t n_cb, uint8_t* d_out, uint64_t* d_status)
+{
+    hipLaunchKernelGGL(rgba ? bu_etc1s_file_kernel<true> : bu_etc1s_file_kernel<false>, dim3(grid), dim3(BU_WG), 0, ctx->stream, d_idx, d_descs, n_slices,
+                       u0, u1, d_ep, n_cb, d_sel, n_cb, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+}
 
 // ---- streamed ETC1S front door -------------------------------------------------------------------------------------------------
 // A slice's symbol stream is serial (one host core: 1.86 ms of BASELINE config 4's 2.6), and everything else used to queue up in
@@ -268,14 +276,8 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     const uint32_t n_cb0 = (uint32_t)n_cb;
     auto launch = [&](uint32_t u0, uint32_t u1) -> bu_status {
         const unsigned grid = bu_grid_for((size_t)(u1 - u0) * 64, ctx->cu_count);
-        if (target == BU_READ_RGBA)
-            hipLaunchKernelGGL(bu_etc1s_file_kernel<true>, dim3(grid), dim3(BU_WG), 0, ctx->stream, static_cast<const uint32_t*>(d_idx_view), d_descs,
-                               (uint32_t)(descs.size() - 1), u0, u1, reinterpret_cast<const uint32_t*>(aux), n_cb0,
-                               reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
-        else
-            hipLaunchKernelGGL(bu_etc1s_file_kernel<false>, dim3(grid), dim3(BU_WG), 0, ctx->stream, static_cast<const uint32_t*>(d_idx_view), d_descs,
-                               (uint32_t)(descs.size() - 1), u0, u1, reinterpret_cast<const uint32_t*>(aux), n_cb0,
-                               reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+        bu_etc1s_file_launch(ctx, target == BU_READ_RGBA, grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(descs.size() - 1), u0, u1,
+                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
         BU_HIP(ctx, hipGetLastError());
         return BU_OK;
     };
@@ -691,14 +693,8 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
             const uint32_t n_cb0 = (uint32_t)lz.endpoints.size();
             const unsigned grid = bu_grid_for((size_t)n_units * 64, ctx->cu_count);
             const BuEtc1sSlice* d_descs = reinterpret_cast<const BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
-            if (target == BU_READ_RGBA)
-                hipLaunchKernelGGL(bu_etc1s_file_kernel<true>, dim3(grid), dim3(BU_WG), 0, ctx->stream, reinterpret_cast<const uint32_t*>(d_in), d_descs,
-                                   (uint32_t)(descs.size() - 1), 0u, n_units, reinterpret_cast<const uint32_t*>(aux), n_cb0,
-                                   reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
-            else
-                hipLaunchKernelGGL(bu_etc1s_file_kernel<false>, dim3(grid), dim3(BU_WG), 0, ctx->stream, reinterpret_cast<const uint32_t*>(d_in), d_descs,
-                                   (uint32_t)(descs.size() - 1), 0u, n_units, reinterpret_cast<const uint32_t*>(aux), n_cb0,
-                                   reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+            bu_etc1s_file_launch(ctx, target == BU_READ_RGBA, grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(descs.size() - 1), 0u, n_units,
+                                 reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
             BU_HIP(ctx, hipGetLastError());
         }
     }

@@ -548,89 +548,23 @@ bu_status bu_transcode_uastc_block_to_etc2(bu_context* ctx, const uint8_t in[16]
 // ---- ETC1S ---------------------------------------------------------------------------------------
 void bu_etc1s_selector_from_rows(const uint8_t rows[4], uint8_t out_entry[8]) { bu_host::selector_from_rows(rows, out_entry); }
 
-// Dynamic LDS above 64 KiB has to be allowed per kernel, once (hipFuncSetAttribute).  May the LDS-staged kernel be used for `lds`
-// bytes of codebooks on this context's device?  The first question per kernel asks the runtime for the most the kernels were
-// measured with (BU_ETC1S_LDS_MAX); a device, partition mode or runtime that refuses is asked again for what the device itself
-// reports (bu_context_create: etc1s_lds_limit); if that fails too the L2-gather kernels serve every size.  The granted size is
-// remembered per kernel in an atomic (the device entry points may be called from several threads; asking twice is harmless):
-// 0 = not asked yet, 1 = refused, otherwise the bytes allowed.
-// Kernel k of the LDS-staged ETC1S kernels: 0 ETC1, 1 RGBA32, 2.. the targets of bu_etc1s_transcode_device (bu_etc1s_target_slot).
-static const void* bu_etc1s_staged_fn(unsigned k)
+// The ETC1S kernels by slot: 0 ETC1, 1 RGBA32, 2.. the targets of bu_etc1s_transcode_device (the numbering of etc1s_lds_state).
+// staged_attr: the slot's LDS-staged kernel as hipFuncSetAttribute takes it; gather / staged: the target slots' kernels as they
+// are launched (the ETC1 and RGBA32 kernels have parameter lists of their own and are named at their launches).
+typedef void (*BuEtc1sTargetFn)(const uint32_t*, const uint32_t*, size_t, const uint32_t*, uint32_t, const uint2*, uint32_t, void*, unsigned long long*,
+                                const BuTablesAll*);
+struct BuEtc1sSlot { const void* staged_attr; BuEtc1sTargetFn gather, staged; };
+static const BuEtc1sSlot& bu_etc1s_slot(unsigned k)
 {
-    static const void* const fns[8] = {
-        reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<false>), reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<true>),
-        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC4, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC5, true>),
-        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_R11, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_RG11, true>),
-        reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC1, true>), reinterpret_cast<const void*>(&bu_etc1s_target_kernel<BU_TGT_BC3, true>)};
-    return fns[k];
+#define BU_SLOT(T) {reinterpret_cast<const void*>(&bu_etc1s_target_kernel<T, true>), &bu_etc1s_target_kernel<T, false>, &bu_etc1s_target_kernel<T, true>}
+    static const BuEtc1sSlot slots[8] = {{reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<false>), nullptr, nullptr},
+                                         {reinterpret_cast<const void*>(&bu_etc1s_staged_kernel<true>), nullptr, nullptr},
+                                         BU_SLOT(BU_TGT_BC4), BU_SLOT(BU_TGT_BC5), BU_SLOT(BU_TGT_R11), BU_SLOT(BU_TGT_RG11), BU_SLOT(BU_TGT_BC1),
+                                         BU_SLOT(BU_TGT_BC3)};
+#undef BU_SLOT
+    return slots[k];
 }
-static bool bu_etc1s_staged_ok(bu_context* ctx, unsigned k, size_t lds)
-{
-    std::atomic<size_t>& state = ctx->etc1s_lds_state[k];
-    size_t s = state.load(std::memory_order_acquire);
-    if (s == 0) {
-        const void* fn = bu_etc1s_staged_fn(k);
-        s = 1;
-        for (const size_t want : {(size_t)BU_ETC1S_LDS_MAX, ctx->etc1s_lds_limit}) {
-            if (want < 4096 || want > BU_ETC1S_LDS_MAX) continue;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess) {
-                s = want;
-                break;
-            }
-            (void)hipGetLastError();  // (not sticky)
-        }
-        state.store(s, std::memory_order_release);
-    }
-    return s > 1 && lds <= s;
-}
-
-bu_status bu_etc1s_transcode_etc1_device(bu_context* ctx, const uint32_t* d_idx, size_t n_blocks, const uint32_t* d_endpoints,
-                                         uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors, void* d_out,
-                                         uint64_t* d_status, void* stream)
-{
-    if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
-    if (n_blocks == 0) return BU_OK;
-    const size_t lds = ((size_t)n_endpoints + n_selectors) * 4;
-    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, 0, lds)) {
-        // codebooks in LDS, one persistent workgroup per CU (with four blocks per lane and step in flight a second workgroup only
-        // doubles the staging: 2^21 blocks 8.0 against 9.3 us, 2^22 12.95 / 13.2, 2^24 37.4 / 39.3)
-        const unsigned per_cu = 1u;
-        hipLaunchKernelGGL(bu_etc1s_staged_kernel<false>, dim3((unsigned)ctx->cu_count * per_cu), dim3(1024), lds, static_cast<hipStream_t>(stream), d_idx,
-                           nullptr, 1u, n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors,
-                           static_cast<uint8_t*>(d_out), reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
-        BU_HIP(ctx, hipGetLastError());
-        return BU_OK;
-    }
-    hipLaunchKernelGGL(bu_etc1s_etc1_kernel, dim3(bu_grid_for(n_blocks, ctx->cu_count)), dim3(BU_WG), 0, static_cast<hipStream_t>(stream), d_idx,
-                       n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors, static_cast<uint2*>(d_out),
-                       reinterpret_cast<unsigned long long*>(d_status));
-    BU_HIP(ctx, hipGetLastError());
-    return BU_OK;
-}
-
-bu_status bu_etc1s_decode_rgba_device(bu_context* ctx, const uint32_t* d_idx, const uint32_t* d_alpha_idx, size_t nbx, size_t nby,
-                                      const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors,
-                                      uint32_t n_selectors, void* d_out, uint64_t* d_status, void* stream)
-{
-    const size_t n_blocks = nbx * nby;
-    if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
-    if (n_blocks == 0) return BU_OK;
-    const size_t lds = ((size_t)n_endpoints + n_selectors + 256) * 4;
-    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, 1, lds)) {
-        hipLaunchKernelGGL(bu_etc1s_staged_kernel<true>, dim3((unsigned)ctx->cu_count), dim3(1024), lds, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx,
-                           (unsigned)nbx, n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors,
-                           static_cast<uint8_t*>(d_out), reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
-        BU_HIP(ctx, hipGetLastError());
-        return BU_OK;
-    }
-    hipLaunchKernelGGL(bu_etc1s_rgba_kernel, dim3(bu_grid_for(n_blocks, ctx->cu_count)), dim3(BU_WG), 0, static_cast<hipStream_t>(stream), d_idx,
-                       d_alpha_idx, (unsigned)nbx, n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors,
-                       static_cast<uint4*>(d_out), reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
-    BU_HIP(ctx, hipGetLastError());
-    return BU_OK;
-}
-
-// the slot of an ETC1S target in bu_etc1s_staged_fn / etc1s_lds_state (2..7), or 0 for a target bu_etc1s_transcode_device refuses
+// the slot of an ETC1S target (2..7), or 0 for a target bu_etc1s_transcode_device refuses
 static unsigned bu_etc1s_target_slot(bu_target target)
 {
     switch (target) {
@@ -644,6 +578,80 @@ static unsigned bu_etc1s_target_slot(bu_target target)
     }
 }
 
+// Dynamic LDS above 64 KiB has to be allowed per kernel, once (hipFuncSetAttribute).  May slot k's LDS-staged kernel use `lds` bytes
+// on this context's device?  The first question per slot asks for the most the kernels were measured with (BU_ETC1S_LDS_MAX); a
+// device, partition mode or runtime that refuses is asked again for what the device itself reports (etc1s_lds_limit); if that fails
+// too the L2-gather kernels serve every size.  The answer is kept per slot in an atomic (the device entry points may be called from
+// several threads; asking twice is harmless): 0 = not asked yet, 1 = refused, otherwise the bytes allowed.
+static bool bu_etc1s_staged_ok(bu_context* ctx, unsigned k, size_t lds)
+{
+    std::atomic<size_t>& state = ctx->etc1s_lds_state[k];
+    size_t s = state.load(std::memory_order_acquire);
+    if (s == 0) {
+        s = 1;
+        for (const size_t want : {(size_t)BU_ETC1S_LDS_MAX, ctx->etc1s_lds_limit}) {
+            if (want < 4096 || want > BU_ETC1S_LDS_MAX) continue;
+            if (hipFuncSetAttribute(bu_etc1s_slot(k).staged_attr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) == hipSuccess) {
+                s = want;
+                break;
+            }
+            (void)hipGetLastError();  // (not sticky)
+        }
+        state.store(s, std::memory_order_release);
+    }
+    return s > 1 && lds <= s;
+}
+
+// The launch shape of slot k for a slice.  Staged from BU_ETC1S_STAGED_MIN blocks where the LDS holds both codebooks (4 bytes per
+// entry) and, for every slot but ETC1, the palette table: one persistent 1024-thread workgroup per CU (ETC1 has four blocks per lane
+// and step in flight; a second workgroup only doubles the staging: 2^21 blocks 8.0 against 9.3 us, 2^22 12.95 / 13.2, 2^24 37.4 /
+// 39.3).  Else the L2 gather: BU_WG-thread workgroups, grid-stride, no dynamic LDS.
+struct BuEtc1sShape { bool staged; dim3 grid, block; size_t lds; };
+static BuEtc1sShape bu_etc1s_shape(bu_context* ctx, unsigned k, size_t n_blocks, uint32_t n_ep, uint32_t n_sel)
+{
+    const size_t lds = ((size_t)n_ep + n_sel + (k == 0 ? 0 : 256)) * 4;
+    if (n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, k, lds)) return {true, dim3((unsigned)ctx->cu_count), dim3(1024), lds};
+    return {false, dim3(bu_grid_for(n_blocks, ctx->cu_count)), dim3(BU_WG), 0};
+}
+
+bu_status bu_etc1s_transcode_etc1_device(bu_context* ctx, const uint32_t* d_idx, size_t n_blocks, const uint32_t* d_endpoints,
+                                         uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors, void* d_out,
+                                         uint64_t* d_status, void* stream)
+{
+    if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
+    if (n_blocks == 0) return BU_OK;
+    const BuEtc1sShape sh = bu_etc1s_shape(ctx, 0, n_blocks, n_endpoints, n_selectors);
+    if (sh.staged)
+        hipLaunchKernelGGL(bu_etc1s_staged_kernel<false>, sh.grid, sh.block, sh.lds, static_cast<hipStream_t>(stream), d_idx, nullptr, 1u, n_blocks,
+                           d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors, static_cast<uint8_t*>(d_out),
+                           reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    else
+        hipLaunchKernelGGL(bu_etc1s_etc1_kernel, sh.grid, sh.block, sh.lds, static_cast<hipStream_t>(stream), d_idx, n_blocks, d_endpoints, n_endpoints,
+                           static_cast<const uint2*>(d_selectors), n_selectors, static_cast<uint2*>(d_out), reinterpret_cast<unsigned long long*>(d_status));
+    BU_HIP(ctx, hipGetLastError());
+    return BU_OK;
+}
+
+bu_status bu_etc1s_decode_rgba_device(bu_context* ctx, const uint32_t* d_idx, const uint32_t* d_alpha_idx, size_t nbx, size_t nby,
+                                      const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors,
+                                      uint32_t n_selectors, void* d_out, uint64_t* d_status, void* stream)
+{
+    const size_t n_blocks = nbx * nby;
+    if (!ctx || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
+    if (n_blocks == 0) return BU_OK;
+    const BuEtc1sShape sh = bu_etc1s_shape(ctx, 1, n_blocks, n_endpoints, n_selectors);
+    if (sh.staged)
+        hipLaunchKernelGGL(bu_etc1s_staged_kernel<true>, sh.grid, sh.block, sh.lds, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx, (unsigned)nbx,
+                           n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors, static_cast<uint8_t*>(d_out),
+                           reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    else
+        hipLaunchKernelGGL(bu_etc1s_rgba_kernel, sh.grid, sh.block, sh.lds, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx, (unsigned)nbx, n_blocks,
+                           d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors, static_cast<uint4*>(d_out),
+                           reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    BU_HIP(ctx, hipGetLastError());
+    return BU_OK;
+}
+
 bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uint32_t* d_idx, const uint32_t* d_alpha_idx, size_t n_blocks,
                                     const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors,
                                     void* d_out, uint64_t* d_status, void* stream)
@@ -652,22 +660,10 @@ bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uin
     if (!ctx || k == 0 || (n_blocks && (!d_idx || !d_endpoints || !d_selectors || !d_out))) return BU_ERR_ARGUMENT;
     if (reinterpret_cast<uintptr_t>(d_out) % bu_target_block_bytes(target)) return BU_ERR_ARGUMENT;
     if (n_blocks == 0) return BU_OK;
-    typedef void (*Fn)(const uint32_t*, const uint32_t*, size_t, const uint32_t*, uint32_t, const uint2*, uint32_t, void*, unsigned long long*,
-                       const BuTablesAll*);
-    static const Fn gather[8] = {nullptr, nullptr, &bu_etc1s_target_kernel<BU_TGT_BC4, false>, &bu_etc1s_target_kernel<BU_TGT_BC5, false>,
-                                 &bu_etc1s_target_kernel<BU_TGT_R11, false>, &bu_etc1s_target_kernel<BU_TGT_RG11, false>,
-                                 &bu_etc1s_target_kernel<BU_TGT_BC1, false>, &bu_etc1s_target_kernel<BU_TGT_BC3, false>};
-    static const Fn staged_fn[8] = {nullptr, nullptr, &bu_etc1s_target_kernel<BU_TGT_BC4, true>, &bu_etc1s_target_kernel<BU_TGT_BC5, true>,
-                                    &bu_etc1s_target_kernel<BU_TGT_R11, true>, &bu_etc1s_target_kernel<BU_TGT_RG11, true>,
-                                    &bu_etc1s_target_kernel<BU_TGT_BC1, true>, &bu_etc1s_target_kernel<BU_TGT_BC3, true>};
-    // both codebooks and the palette table in LDS from BU_ETC1S_STAGED_MIN blocks (the rule of the ETC1 and RGBA32 calls), one
-    // persistent workgroup per CU
-    const size_t lds = ((size_t)n_endpoints + n_selectors + 256) * 4;
-    const bool staged = n_blocks >= BU_ETC1S_STAGED_MIN && bu_etc1s_staged_ok(ctx, k, lds);
-    hipLaunchKernelGGL(staged ? staged_fn[k] : gather[k],
-                       dim3(staged ? (unsigned)ctx->cu_count : bu_grid_for(n_blocks, ctx->cu_count)), dim3(staged ? 1024 : BU_WG),
-                       staged ? lds : 0, static_cast<hipStream_t>(stream), d_idx, d_alpha_idx, n_blocks, d_endpoints, n_endpoints,
-                       static_cast<const uint2*>(d_selectors), n_selectors, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    const BuEtc1sShape sh = bu_etc1s_shape(ctx, k, n_blocks, n_endpoints, n_selectors);
+    hipLaunchKernelGGL(sh.staged ? bu_etc1s_slot(k).staged : bu_etc1s_slot(k).gather, sh.grid, sh.block, sh.lds, static_cast<hipStream_t>(stream), d_idx,
+                       d_alpha_idx, n_blocks, d_endpoints, n_endpoints, static_cast<const uint2*>(d_selectors), n_selectors, d_out,
+                       reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
     BU_HIP(ctx, hipGetLastError());
     return BU_OK;
 }

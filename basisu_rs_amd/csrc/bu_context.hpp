@@ -50,8 +50,8 @@ struct bu_context {
     std::atomic<int> time_enqueue_threads{0};  // bu_time_set_enqueue_threads: the streams windows enqueue from one host thread per stream
     std::atomic<bool> block_api_on_device{false};  // per-block API: host build of the block code (default) or a 1-block launch
     size_t etc1s_lds_limit = 0;  // what the device reports a workgroup may use, less a margin (bu_context_create)
-    // bu_etc1s_staged_kernel<false / true>, then bu_etc1s_target_kernel<BC4, BC5, R11, RG11, BC1, BC3; true> (bu_etc1s_staged_fn):
-    // 0 not asked, 1 refused, else dynamic LDS bytes granted
+    // per slot of the ETC1S kernel table (bu_etc1s_slot, bu_capi_slice.hpp: ETC1, RGBA32, BC4, BC5, R11, RG11, BC1, BC3), for the slot's
+    // LDS-staged kernel: 0 not asked, 1 refused, else dynamic LDS bytes granted
     std::atomic<size_t> etc1s_lds_state[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
     std::mutex stream_lock;  // creation of extra_streams (bu_ctx_streams)
     std::mutex lock;  // host-pointer entry points share the staging buffers

@@ -1,4 +1,6 @@
-// ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / EAC RG11 for the gfx950 kernels, in palette form.
+// The per-block code of the ETC1S back end for the gfx950 kernels (bu_etc1s_kernels.hpp) and, compiled for the host, for the CPU tests
+// (tests/host_emul/bu_emul_etc1s.cpp): ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / EAC RG11 in palette form and,
+// at the end, the pieces every ETC1S kernel shares -- palettes, index split and check, the ETC1 block, the RGBA32 block.
 // The output of every target is the rule of DESIGN.md section 4.4 / 4.5 applied to the block that BU_TARGET_RGBA32 decodes
 // (bu_etc1s_block_rgba): the 16-texel encoders of bu_uastc_channel.hpp / bu_uastc_colour.hpp, bit for bit.  An ETC1S block holds
 // at most four colours -- one etc1s_pal word per channel, byte s = the value of selector s -- and a 2-bit selector per texel, texel
@@ -337,4 +339,59 @@ BU_DEV void bu_etc1s_palettes(const uint32_t* pal, uint32_t ep, uint32_t aep, ui
     pg = pal[it | ((ep >> 8) & 31u)];
     pb = pal[it | ((ep >> 16) & 31u)];
     pa = pal[((aep >> 19) & 0xE0u) | ((aep >> 8) & 31u)];
+}
+
+// ---- the pieces every ETC1S kernel shares ---------------------------------------------------------------------------------------
+// The index words of one block: ix = endpoint index | selector index << 16 of the colour slice, ax the same of the alpha slice
+// (read only with has_a); bad = some index lies outside its codebook.
+struct BuEtc1sIndex {
+    uint32_t e, s, ae, as;
+    bool bad;
+};
+BU_DEV BuEtc1sIndex bu_etc1s_index(uint32_t ix, bool has_a, uint32_t ax, uint32_t n_ep, uint32_t n_sel)
+{
+    BuEtc1sIndex k;
+    k.e = ix & 0xFFFFu;
+    k.s = ix >> 16;
+    k.ae = has_a ? ax & 0xFFFFu : 0u;
+    k.as = has_a ? ax >> 16 : 0u;
+    k.bad = k.e >= n_ep || k.s >= n_sel || (has_a && (k.ae >= n_ep || k.as >= n_sel));
+    return k;
+}
+
+// ETC1 of one block (basis_lz/mod.rs:163-181): the endpoint word's 5-bit colours as bytes r5 << 3, g5 << 3, b5 << 3 and the
+// intensity twice, inten << 5 | inten << 2 | 0b11 (u8 arithmetic); sel_y = the selector entry's second word, the ETC1 selector bytes.
+BU_DEV void bu_etc1s_etc1_block(uint32_t ep, uint32_t sel_y, uint32_t out[2])
+{
+    const uint32_t inten = ep >> 24;
+    out[0] = ((ep << 3) & 0x00F8F8F8u) | ((((inten << 5) | (inten << 2) | 3u) & 0xFFu) << 24);
+    out[1] = sel_y;
+}
+
+// RGBA32 of one block (basis_lz/mod.rs:122-146): 16 texels = colours[selector] of the colour endpoint, alpha = colours[selector].g of
+// the alpha slice's endpoint (:139-143), from the palette words of bu_etc1s_palettes.  The selectors of a block COLUMN are
+// byte-aligned -- texel (x, y) sits at bits 8y + 2x of `rows` (etc.rs:354-361), so (rows >> 2x) & 0x03030303 is the column's four
+// selectors, one per byte: exactly a v_perm_b32 selector.  One v_perm per channel and column looks the four texels up, two levels
+// of byte permutes turn the channel columns into texel words (round 2: sixteen four-way select chains per plane).
+BU_DEV void bu_etc1s_block_rgba(uint32_t pr, uint32_t pg, uint32_t pb, uint32_t pa, uint32_t rows, bool has_a, uint32_t arows, uint32_t px[16])
+{
+    BU_UNROLL
+    for (int x = 0; x < 4; x++) {
+        const uint32_t sel = (rows >> (2 * x)) & 0x03030303u;
+        const uint32_t r = bu_perm(0u, pr, sel), g = bu_perm(0u, pg, sel), b = bu_perm(0u, pb, sel);
+        const uint32_t t01 = bu_perm(g, r, 0x05010400u), t23 = bu_perm(g, r, 0x07030602u);  // R0 G0 R1 G1 / R2 G2 R3 G3
+        if (has_a) {
+            const uint32_t a = bu_perm(0u, pa, (arows >> (2 * x)) & 0x03030303u);
+            const uint32_t u01 = bu_perm(a, b, 0x05010400u), u23 = bu_perm(a, b, 0x07030602u);
+            px[x] = bu_perm(u01, t01, 0x05040100u);
+            px[4 + x] = bu_perm(u01, t01, 0x07060302u);
+            px[8 + x] = bu_perm(u23, t23, 0x05040100u);
+            px[12 + x] = bu_perm(u23, t23, 0x07060302u);
+        } else {
+            px[x] = bu_perm(b, t01, 0x0D040100u);  // R G B 255
+            px[4 + x] = bu_perm(b, t01, 0x0D050302u);
+            px[8 + x] = bu_perm(b, t23, 0x0D060100u);
+            px[12 + x] = bu_perm(b, t23, 0x0D070302u);
+        }
+    }
 }

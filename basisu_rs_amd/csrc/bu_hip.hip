@@ -34,10 +34,11 @@
 #include "bu_basis.hpp"
 #include "bu_batch_plan.hpp"   // slices -> runs -> launches of the batch entry points (host only)
 #include "bu_uastc_dispatch.hpp"
-#include "bu_etc1s_targets.hpp"   // ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 per block (palette form)
+#include "bu_etc1s_targets.hpp"   // ETC1S per block: index check, ETC1, RGBA32, BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 (palette form)
 #include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 
-#include "bu_kernels.hpp"        // device code
+#include "bu_kernels.hpp"        // device code: UASTC, status reset, CRC, sleep, copy
+#include "bu_etc1s_kernels.hpp"  // device code: the ETC1S back end
 #include "bu_context.hpp"        // bu_context, launcher, host-pointer driver
 #include "bu_streams.hpp"        // the context's own streams (hardware-queue check), BU_LAUNCH_AUTO
 #include "bu_capi_slice.hpp"     // extern "C": slice level

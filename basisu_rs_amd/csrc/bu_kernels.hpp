@@ -1,5 +1,5 @@
 // gfx950 kernels of the block-transcode path: the one-lane-per-block kernel, the mode-sorted kernel (every UASTC target), the
-// ETC1S codebook-lookup kernels, the status-word reset and the copy kernel of the measurement harness.
+// status-word reset, the CRC, sleep and copy kernels (the ETC1S codebook-lookup kernels: bu_etc1s_kernels.hpp).
 // Part of the single translation unit bu_hip.hip (included there; not a stand-alone header).
 #pragma once
 namespace {
@@ -689,374 +689,6 @@ __global__ __launch_bounds__(WG) void bu_copy_kernel(const uint4* __restrict__ i
             bu_v4u r;
             r.x = v[k].x; r.y = v[k].y; r.z = v[k].z; r.w = v[k].w;
             __builtin_nontemporal_store(r, reinterpret_cast<bu_v4u*>(out + i));
-        }
-    }
-}
-
-// ---- ETC1S back-end ----------------------------------------------------------------------------
-// basis_lz/mod.rs:122-146 for one block: 16 texels = colours[selector] of the colour endpoint, alpha = colours[selector].g of the
-// alpha slice's endpoint (:139-143).  Byte palettes: a channel's four colours are one etc1s_pal word (etc.rs:396-431 tabulated),
-// and the selectors of a block COLUMN are byte-aligned -- texel (x, y) sits at bits 8y + 2x of `rows` (etc.rs:354-361), so
-// (rows >> 2x) & 0x03030303 is the column's four selectors, one per byte: exactly a v_perm_b32 selector.  One v_perm per channel
-// and column looks the four texels up, two levels of byte permutes turn the channel columns into texel words (round 2: sixteen
-// four-way select chains per plane).
-__device__ __forceinline__ void bu_etc1s_block_rgba(const uint32_t* pal_lut, uint32_t ep, uint32_t rows, bool has_a, uint32_t aep, uint32_t arows,
-                                                    uint32_t px[16])
-{
-    const uint32_t it = (ep >> 19) & 0xE0u;  // inten << 5
-    const uint32_t pr = pal_lut[it | (ep & 31u)], pg = pal_lut[it | ((ep >> 8) & 31u)], pb = pal_lut[it | ((ep >> 16) & 31u)];
-    uint32_t pa = 0;
-    if (has_a) pa = pal_lut[((aep >> 19) & 0xE0u) | ((aep >> 8) & 31u)];  // .a = colors[sel].g of the alpha endpoint
-#pragma unroll
-    for (int x = 0; x < 4; x++) {
-        const uint32_t sel = (rows >> (2 * x)) & 0x03030303u;
-        const uint32_t r = bu_perm(0u, pr, sel), g = bu_perm(0u, pg, sel), b = bu_perm(0u, pb, sel);
-        const uint32_t t01 = bu_perm(g, r, 0x05010400u), t23 = bu_perm(g, r, 0x07030602u);  // R0 G0 R1 G1 / R2 G2 R3 G3
-        if (has_a) {
-            const uint32_t a = bu_perm(0u, pa, (arows >> (2 * x)) & 0x03030303u);
-            const uint32_t u01 = bu_perm(a, b, 0x05010400u), u23 = bu_perm(a, b, 0x07030602u);
-            px[x] = bu_perm(u01, t01, 0x05040100u);
-            px[4 + x] = bu_perm(u01, t01, 0x07060302u);
-            px[8 + x] = bu_perm(u23, t23, 0x05040100u);
-            px[12 + x] = bu_perm(u23, t23, 0x07060302u);
-        } else {
-            px[x] = bu_perm(b, t01, 0x0D040100u);  // R G B 255
-            px[4 + x] = bu_perm(b, t01, 0x0D050302u);
-            px[8 + x] = bu_perm(b, t23, 0x0D060100u);
-            px[12 + x] = bu_perm(b, t23, 0x0D070302u);
-        }
-    }
-}
-
-// basis_lz/mod.rs:163-181
-__global__ __launch_bounds__(BU_WG) void bu_etc1s_etc1_kernel(const uint32_t* __restrict__ idx, size_t n_blocks,
-                                                              const uint32_t* __restrict__ endpoints, uint32_t n_ep,
-                                                              const uint2* __restrict__ selectors, uint32_t n_sel,
-                                                              uint2* __restrict__ out, unsigned long long* status)
-{
-    const size_t stride = (size_t)gridDim.x * BU_WG;
-    for (size_t i = (size_t)blockIdx.x * BU_WG + threadIdx.x; i < n_blocks; i += stride) {
-        const uint32_t ix = __builtin_nontemporal_load(idx + i);  // streamed once; the codebook gathers below stay cached
-        const uint32_t e = ix & 0xFFFFu, s = ix >> 16;
-        uint2 o = make_uint2(0, 0);
-        if (e >= n_ep || s >= n_sel) {
-            bu_report(status, i, BU_ERR_INDEX_RANGE);
-        } else {
-            const uint32_t ep = endpoints[e];
-            const uint32_t inten = ep >> 24;
-            // bytes: r5<<3, g5<<3, b5<<3, inten<<5 | inten<<2 | 0b11 (u8 arithmetic)
-            o.x = ((ep << 3) & 0x00F8F8F8u) | ((((inten << 5) | (inten << 2) | 3u) & 0xFFu) << 24);
-            o.y = selectors[s].y;
-        }
-        bu_st_stream(out + i, o);
-    }
-}
-
-// basis_lz/mod.rs:122-146 (+ the alpha pass :139-143 fused)
-__global__ __launch_bounds__(BU_WG) void bu_etc1s_rgba_kernel(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ aidx,
-                                                              unsigned nbx, size_t n_blocks, const uint32_t* __restrict__ endpoints,
-                                                              uint32_t n_ep, const uint2* __restrict__ selectors, uint32_t n_sel,
-                                                              uint4* __restrict__ out, unsigned long long* status,
-                                                              const BuTablesAll* __restrict__ tables)
-{
-    __shared__ uint32_t pal_lut[256];
-    pal_lut[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
-    static_assert(BU_WG == 256, "one palette word per thread");
-    __syncthreads();
-    const size_t stride = (size_t)gridDim.x * BU_WG;
-    for (size_t i = (size_t)blockIdx.x * BU_WG + threadIdx.x; i < n_blocks; i += stride) {
-        const uint32_t ix = __builtin_nontemporal_load(idx + i);
-        const uint32_t e = ix & 0xFFFFu, s = ix >> 16;
-        uint32_t ae = 0, as = 0;
-        bool bad = e >= n_ep || s >= n_sel;
-        if (aidx) {
-            const uint32_t ax = __builtin_nontemporal_load(aidx + i);
-            ae = ax & 0xFFFFu;
-            as = ax >> 16;
-            bad = bad || ae >= n_ep || as >= n_sel;
-        }
-        uint32_t px[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) px[k] = 0;
-        if (bad) {
-            bu_report(status, i, BU_ERR_INDEX_RANGE);
-        } else {
-            const uint32_t ep = endpoints[e], rows = selectors[s].x;
-            uint32_t aep = 0, arows = 0;
-            if (aidx) {
-                aep = endpoints[ae];
-                arows = selectors[as].x;
-            }
-            bu_etc1s_block_rgba(pal_lut, ep, rows, aidx != nullptr, aep, arows, px);
-        }
-        const size_t by = i / nbx, bx = i - by * nbx;
-#pragma unroll
-        for (int r = 0; r < 4; r++) bu_st_stream(out + (4 * by + r) * (size_t)nbx + bx, make_uint4(px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]));
-    }
-}
-
-
-// ---- large slices: both codebooks staged in LDS -------------------------------------------------------------------------------
-// One persistent 1024-thread workgroup per CU (two where they fit) copies the endpoint codebook (4 B per entry) and the half of the
-// selector codebook its target reads (4 B per entry: texel rows for RGBA32, ETC1 selector bytes for ETC1) into dynamic LDS and
-// walks the slice with LDS lookups.  Against the L2 gather above (tools/exp/etc1s_sweep.py, 4096 + 8192 entries, cold rotation):
-// 2^18 blocks 4.3 / 5.4 us against 4.3 / 5.0 (ETC1 / RGBA32: launch-bound either way), 2^20 6.7 / 16.0 against 10.3 / 23.3,
-// 2^22 15.8 / 56.1 against 38.7 / 91.8, 2^24 41.6 / 218 against 147 / 366 us (ETC1 at 4.8 TB/s, RGBA32 at 5.2 TB/s): the gather
-// is bound by the L2's random 4- and 8-byte reads, not by HBM.  The launcher takes this kernel from 2^19 blocks up.
-template <bool RGBA>
-__global__ __launch_bounds__(1024) void bu_etc1s_staged_kernel(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ aidx, unsigned nbx,
-                                                               size_t n_blocks, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
-                                                               const uint2* __restrict__ selectors, uint32_t n_sel, uint8_t* __restrict__ out,
-                                                               unsigned long long* status, const BuTablesAll* __restrict__ tables)
-{
-    extern __shared__ uint32_t bu_etc1s_lds[];
-    uint32_t* s_ep = bu_etc1s_lds;
-    uint32_t* s_sel = bu_etc1s_lds + n_ep;
-    uint32_t* pal_lut = s_sel + n_sel;
-    const size_t stride = (size_t)gridDim.x * 1024, first = (size_t)blockIdx.x * 1024 + threadIdx.x;
-    // ETC1, index array 8-byte and output 16-byte aligned: FOUR blocks per lane and step, a wave on 256 consecutive blocks -- the
-    // lane's blocks 2L, 2L+1 and 128+2L, 128+2L+1, so that both of its 8-byte index loads and both of its 16-byte result stores
-    // are contiguous across the wave (512 B / 1 KiB per instruction; four CONSECUTIVE blocks per lane make every store
-    // instruction write half of each cache line: 2^22 blocks 16 -> 31 us) -- with the next step's indices already in flight.
-    // The first loads are issued BEFORE the codebooks are staged, so their latency hides behind the staging.
-    const bool vec4 = !RGBA && (reinterpret_cast<uintptr_t>(idx) & 7u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-    const size_t n256 = vec4 ? n_blocks / 256 : 0, wstride = stride / 64, wfirst = first / 64;  // 256-block chunks; waves
-    const uint2* idx2 = reinterpret_cast<const uint2*>(idx);
-    const unsigned lane = threadIdx.x & 63u;
-    bu_v2u curA = {0, 0}, curB = {0, 0};
-    uint32_t cur = 0, acur = 0;
-    if (vec4) {
-        if (wfirst < n256) {
-            curA = __builtin_nontemporal_load(reinterpret_cast<const bu_v2u*>(idx2 + wfirst * 128 + lane));
-            curB = __builtin_nontemporal_load(reinterpret_cast<const bu_v2u*>(idx2 + wfirst * 128 + 64 + lane));
-        }
-    } else if (first < n_blocks) {
-        cur = __builtin_nontemporal_load(idx + first);
-        if (RGBA && aidx) acur = __builtin_nontemporal_load(aidx + first);
-    }
-    // staging, 16 bytes per load where the source allows (selectors: two 8-byte entries, of which the target keeps 4 bytes each)
-    if ((reinterpret_cast<uintptr_t>(endpoints) & 15u) == 0) {
-        for (uint32_t i = threadIdx.x; i < n_ep / 4; i += 1024) reinterpret_cast<uint4*>(s_ep)[i] = reinterpret_cast<const uint4*>(endpoints)[i];
-        for (uint32_t i = (n_ep & ~3u) + threadIdx.x; i < n_ep; i += 1024) s_ep[i] = endpoints[i];
-    } else {
-        for (uint32_t i = threadIdx.x; i < n_ep; i += 1024) s_ep[i] = endpoints[i];
-    }
-    if ((reinterpret_cast<uintptr_t>(selectors) & 15u) == 0 && (n_ep & 1u) == 0) {
-        for (uint32_t i = threadIdx.x; i < n_sel / 2; i += 1024) {
-            const uint4 two = reinterpret_cast<const uint4*>(selectors)[i];
-            reinterpret_cast<uint2*>(s_sel)[i] = RGBA ? make_uint2(two.x, two.z) : make_uint2(two.y, two.w);
-        }
-        if ((n_sel & 1u) && threadIdx.x == 0) s_sel[n_sel - 1] = RGBA ? selectors[n_sel - 1].x : selectors[n_sel - 1].y;
-    } else {
-        for (uint32_t i = threadIdx.x; i < n_sel; i += 1024) s_sel[i] = RGBA ? selectors[i].x : selectors[i].y;
-    }
-    if (RGBA && threadIdx.x < 256) pal_lut[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
-    __syncthreads();
-    // basis_lz/mod.rs:163-181 for one block
-    auto etc1_block = [&](uint32_t ix, size_t i) {
-        const uint32_t e = ix & 0xFFFFu, sl = ix >> 16;
-        uint2 o = make_uint2(0, 0);
-        if (e >= n_ep || sl >= n_sel) {
-            bu_report(status, i, BU_ERR_INDEX_RANGE);
-        } else {
-            const uint32_t ep = s_ep[e], inten = ep >> 24;
-            o.x = ((ep << 3) & 0x00F8F8F8u) | ((((inten << 5) | (inten << 2) | 3u) & 0xFFu) << 24);
-            o.y = s_sel[sl];
-        }
-        return o;
-    };
-    if (vec4) {
-        for (size_t w = wfirst; w < n256; w += wstride) {
-            const size_t wn = w + wstride;
-            bu_v2u nxtA = {0, 0}, nxtB = {0, 0};
-            if (wn < n256) {
-                nxtA = __builtin_nontemporal_load(reinterpret_cast<const bu_v2u*>(idx2 + wn * 128 + lane));
-                nxtB = __builtin_nontemporal_load(reinterpret_cast<const bu_v2u*>(idx2 + wn * 128 + 64 + lane));
-            }
-            const size_t i0 = w * 256 + 2 * lane;
-            const uint2 a = etc1_block(curA.x, i0), b = etc1_block(curA.y, i0 + 1), c = etc1_block(curB.x, i0 + 128), d = etc1_block(curB.y, i0 + 129);
-            uint4* o4 = reinterpret_cast<uint4*>(out) + w * 128 + lane;
-            bu_st_stream(o4, make_uint4(a.x, a.y, b.x, b.y));
-            bu_st_stream(o4 + 64, make_uint4(c.x, c.y, d.x, d.y));
-            curA = nxtA;
-            curB = nxtB;
-        }
-        // the last n_blocks % 256 blocks
-        const size_t t = 256 * n256 + first;
-        if (t < n_blocks) bu_st_stream(reinterpret_cast<uint2*>(out) + t, etc1_block(__builtin_nontemporal_load(idx + t), t));
-        return;
-    }
-    for (size_t i = first; i < n_blocks; i += stride) {
-        const size_t in = i + stride;
-        uint32_t nxt = 0, anxt = 0;
-        if (in < n_blocks) {
-            nxt = __builtin_nontemporal_load(idx + in);
-            if (RGBA && aidx) anxt = __builtin_nontemporal_load(aidx + in);
-        }
-        if constexpr (!RGBA) {
-            bu_st_stream(reinterpret_cast<uint2*>(out) + i, etc1_block(cur, i));
-        } else {  // basis_lz/mod.rs:122-146
-            const uint32_t e = cur & 0xFFFFu, sl = cur >> 16, ae = acur & 0xFFFFu, as = acur >> 16;
-            const bool bad = e >= n_ep || sl >= n_sel || (aidx && (ae >= n_ep || as >= n_sel));
-            uint32_t px[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) px[k] = 0;
-            if (bad) bu_report(status, i, BU_ERR_INDEX_RANGE);
-            else bu_etc1s_block_rgba(pal_lut, s_ep[e], s_sel[sl], aidx != nullptr, aidx ? s_ep[ae] : 0u, aidx ? s_sel[as] : 0u, px);
-            const size_t by = i / nbx, bx = i - by * nbx;
-            uint4* img = reinterpret_cast<uint4*>(out);
-#pragma unroll
-            for (int r = 0; r < 4; r++) bu_st_stream(img + (4 * by + r) * (size_t)nbx + bx, make_uint4(px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]));
-        }
-        cur = nxt;
-        acur = anxt;
-    }
-}
-// blocks from which the staged kernel is launched, and the LDS one CU can give a workgroup (160 KiB less a margin)
-constexpr size_t BU_ETC1S_STAGED_MIN = (size_t)1 << 19, BU_ETC1S_LDS_MAX = 152 * 1024;
-
-// ---- ETC1S -> BC1 / BC3 / BC4 / BC5 / EAC R11 / EAC RG11 (bu_etc1s_targets.hpp) ---------------------------
-// One lane per block and step, grid-stride, the next step's indices in flight.  STAGED = false: the L2 gather of the kernels above,
-// 256-thread workgroups, the palette table in LDS.  STAGED = true: one persistent 1024-thread workgroup per CU with both codebooks
-// (endpoint words, selector rows) and the palette table in dynamic LDS, as bu_etc1s_staged_kernel<true> lays them out.  A wave's 64
-// lanes hold 64 consecutive blocks, so each result store instruction writes 512 B (8-byte targets) or 1 KiB contiguous: whole cache
-// lines for an output aligned to them.  Index errors report as the RGBA32 kernels do and leave a zero block.
-template <int TARGET, bool STAGED>
-__global__ __launch_bounds__(STAGED ? 1024 : BU_WG) void bu_etc1s_target_kernel(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ aidx,
-                                                                                size_t n_blocks, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
-                                                                                const uint2* __restrict__ selectors, uint32_t n_sel,
-                                                                                void* __restrict__ out, unsigned long long* status,
-                                                                                const BuTablesAll* __restrict__ tables)
-{
-    constexpr unsigned WGS = STAGED ? 1024u : (unsigned)BU_WG;
-    extern __shared__ uint32_t bu_etc1s_tgt_lds[];
-    __shared__ uint32_t s_pal_static[STAGED ? 1 : 256];
-    uint32_t* s_ep = bu_etc1s_tgt_lds;
-    uint32_t* s_sel = bu_etc1s_tgt_lds + n_ep;
-    uint32_t* pal = STAGED ? s_sel + n_sel : s_pal_static;
-    const size_t stride = (size_t)gridDim.x * WGS, first = (size_t)blockIdx.x * WGS + threadIdx.x;
-    uint32_t cur = 0, acur = 0;
-    if (first < n_blocks) {
-        cur = __builtin_nontemporal_load(idx + first);
-        if (aidx) acur = __builtin_nontemporal_load(aidx + first);
-    }
-    if constexpr (STAGED) {
-        for (uint32_t i = threadIdx.x; i < n_ep; i += WGS) s_ep[i] = endpoints[i];
-        for (uint32_t i = threadIdx.x; i < n_sel; i += WGS) s_sel[i] = selectors[i].x;
-    }
-    if (threadIdx.x < 256) pal[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
-    __syncthreads();
-    const BuTables& T = tables->t;  // (R11 / RG11: the EAC tables, read through the scalar cache in the table search)
-    for (size_t i = first; i < n_blocks; i += stride) {
-        const size_t in = i + stride;
-        uint32_t nxt = 0, anxt = 0;
-        if (in < n_blocks) {
-            nxt = __builtin_nontemporal_load(idx + in);
-            if (aidx) anxt = __builtin_nontemporal_load(aidx + in);
-        }
-        const uint32_t e = cur & 0xFFFFu, sl = cur >> 16, ae = acur & 0xFFFFu, as = acur >> 16;
-        const bool bad = e >= n_ep || sl >= n_sel || (aidx && (ae >= n_ep || as >= n_sel));
-        uint32_t o[4] = {0, 0, 0, 0};
-        if (bad) {
-            bu_report(status, i, BU_ERR_INDEX_RANGE);
-        } else {
-            const uint32_t ep = STAGED ? s_ep[e] : endpoints[e], rows = STAGED ? s_sel[sl] : selectors[sl].x;
-            uint32_t aep = 0, arows = 0;
-            if (aidx) {
-                aep = STAGED ? s_ep[ae] : endpoints[ae];
-                arows = STAGED ? s_sel[as] : selectors[as].x;
-            }
-            uint32_t pr, pg, pb, pa;
-            bu_etc1s_palettes(pal, ep, aep, pr, pg, pb, pa);
-            bu_etc1s_target_block<TARGET>(T, pr, pg, pb, rows, aidx != nullptr, pa, arows, o);
-        }
-        if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out) + i, make_uint2(o[0], o[1]));
-        else bu_st_stream(reinterpret_cast<uint4*>(out) + i, make_uint4(o[0], o[1], o[2], o[3]));
-        cur = nxt;
-        acur = anxt;
-    }
-}
-
-// ---- whole-file ETC1S launches (bu_read_to): every slice of the file in ONE launch -----------------------------------
-// The host concatenates the per-slice index arrays (each padded to a multiple of 64 words) and describes the slices in a
-// small table; a wave owns one 64-block unit, finds its slice by a scalar binary search over the units' prefix and then
-// does exactly what the per-slice kernels do.  One status word per image, as the sequential drivers report.
-struct BuEtc1sSlice {
-    uint32_t unit0;     // first 64-block unit of this slice (the table ends with a sentinel holding the total)
-    uint32_t n_blocks;  // nbx * nby
-    uint32_t nbx;       // blocks per row (RGBA addressing)
-    uint32_t idx_ofs;   // colour indices, in words from the start of the staged index buffer
-    uint32_t aidx_ofs;  // alpha indices (RGBA with alpha pairs), 0xFFFFFFFF = none
-    uint32_t image;     // status word / image number
-    uint64_t out_ofs;   // byte offset of the image in the output buffer
-};
-static_assert(sizeof(BuEtc1sSlice) == 32, "descriptor layout is shared with the host code");
-
-template <bool RGBA>
-__global__ __launch_bounds__(BU_WG) void bu_etc1s_file_kernel(const uint32_t* __restrict__ idx, const BuEtc1sSlice* __restrict__ slices, uint32_t n_slices,
-                                                              uint32_t unit_begin, uint32_t n_units, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
-                                                              const uint2* __restrict__ selectors, uint32_t n_sel, uint8_t* __restrict__ out,
-                                                              unsigned long long* status, const BuTablesAll* __restrict__ tables)
-{
-    __shared__ uint32_t pal_lut[RGBA ? 256 : 1];
-    if constexpr (RGBA) {
-        pal_lut[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
-        __syncthreads();
-    }
-    const uint32_t lane = threadIdx.x & 63u, wpg = BU_WG / 64;
-    // units [unit_begin, n_units) of the file: the streamed front door launches the bands of a slice as their rows are decoded
-    for (uint32_t unit = unit_begin + blockIdx.x * wpg + (threadIdx.x >> 6); unit < n_units; unit += gridDim.x * wpg) {
-        // largest s with slices[s].unit0 <= unit (unit is wave-uniform: the search runs on the scalar unit)
-        uint32_t lo = 0, hi = n_slices;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if ((uint32_t)__builtin_amdgcn_readfirstlane((int)slices[mid].unit0) <= unit) lo = mid;
-            else hi = mid;
-        }
-        const BuEtc1sSlice sd = slices[lo];
-        const uint32_t i = (unit - sd.unit0) * 64u + lane;
-        if (i >= sd.n_blocks) continue;
-        const uint32_t ix = __builtin_nontemporal_load(idx + sd.idx_ofs + i);
-        const uint32_t e = ix & 0xFFFFu, sl = ix >> 16;
-        bool bad = e >= n_ep || sl >= n_sel;
-        if constexpr (!RGBA) {
-            uint2 o = make_uint2(0, 0);
-            if (bad) {
-                bu_report(status + sd.image, i, BU_ERR_INDEX_RANGE);
-            } else {  // basis_lz/mod.rs:163-181
-                const uint32_t ep = endpoints[e];
-                const uint32_t inten = ep >> 24;
-                o.x = ((ep << 3) & 0x00F8F8F8u) | ((((inten << 5) | (inten << 2) | 3u) & 0xFFu) << 24);
-                o.y = selectors[sl].y;
-            }
-            bu_st_stream(reinterpret_cast<uint2*>(out + sd.out_ofs) + i, o);
-        } else {  // basis_lz/mod.rs:122-146
-            const bool has_a = sd.aidx_ofs != 0xFFFFFFFFu;
-            uint32_t ae = 0, as = 0;
-            if (has_a) {
-                const uint32_t ax = __builtin_nontemporal_load(idx + sd.aidx_ofs + i);
-                ae = ax & 0xFFFFu;
-                as = ax >> 16;
-                bad = bad || ae >= n_ep || as >= n_sel;
-            }
-            uint32_t px[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) px[k] = 0;
-            if (bad) {
-                bu_report(status + sd.image, i, BU_ERR_INDEX_RANGE);
-            } else {
-                const uint32_t ep = endpoints[e], rows = selectors[sl].x;
-                uint32_t aep = 0, arows = 0;
-                if (has_a) {
-                    aep = endpoints[ae];
-                    arows = selectors[as].x;
-                }
-                bu_etc1s_block_rgba(pal_lut, ep, rows, has_a, aep, arows, px);
-            }
-            const uint32_t by = i / sd.nbx, bx = i - by * sd.nbx;
-            uint4* img = reinterpret_cast<uint4*>(out + sd.out_ofs);
-#pragma unroll
-            for (int r = 0; r < 4; r++) bu_st_stream(img + (size_t)(4 * by + r) * sd.nbx + bx, make_uint4(px[4 * r], px[4 * r + 1], px[4 * r + 2], px[4 * r + 3]));
         }
     }
 }

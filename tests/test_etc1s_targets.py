@@ -1,6 +1,7 @@
 """ETC1S -> BC1, BC3, BC4, BC5, EAC R11 and EAC RG11 on the CPU: the host build of the palette-form encoders (bu_etc1s_targets.hpp,
 DESIGN.md section 4.6) against the numpy models of tests/colour_model.py and tests/channel_model.py, applied to the oracle's RGBA32
-decode of the same blocks (oracle/bu_oracle.c), so neither side of the comparison borrows the kernel's own palette or masks.
+decode of the same blocks (oracle/bu_oracle.c), so neither side of the comparison borrows the kernel's own palette or masks.  The ETC1
+and RGBA32 blocks and the index check of the same header, which every ETC1S kernel shares, are compared with the oracle directly.
 
 Three sets: every palette word of one channel under every non-empty set of used selectors (BC4, R11), random blocks for every target,
 and a mined set that reaches every edge class of the BC1 rule a palette can take."""
@@ -20,6 +21,7 @@ HOST_EMUL = os.path.join(ROOT, "tests", "host_emul")
 CSRC = os.path.join(ROOT, "basisu_rs_amd", "csrc")
 # name -> (bu_target, bytes per block)
 TARGETS = {"bc1": (11, 8), "bc3": (12, 16), "bc4": (6, 8), "bc5": (7, 16), "r11": (8, 8), "rg11": (9, 16)}
+BASE = {"etc1": (2, 8), "rgba": (4, 64)}  # the two targets of the ETC1S back end that the oracle itself writes
 N_RANDOM = 200_000
 CHUNK = 32768  # blocks per oracle call: a codebook entry per block and per slice, indices below 2^16
 MINE_K = 64
@@ -167,27 +169,31 @@ for k in sorted({f.split("/")[0] for f in sets.files}):
     aep, arows = (sets[k + "/aep"], sets[k + "/arows"]) if alpha else (None, None)
     for name, (t, bb) in %r.items():
         out = np.zeros((ep.size, bb), dtype=np.uint8)
-        assert lib.bu_emul_etc1s_batch(t, ep.ctypes.data, rows.ctypes.data, None if aep is None else aep.ctypes.data,
+        sel = sets[k + "/sely"] if name == "etc1" else rows  # the word of the selector entry the target reads
+        assert lib.bu_emul_etc1s_batch(t, ep.ctypes.data, sel.ctypes.data, None if aep is None else aep.ctypes.data,
                                        None if arows is None else arows.ctypes.data, ep.size, out.ctypes.data) == 0
         res[k + "/" + name] = out
 o = np.zeros((1, 16), dtype=np.uint8)
-for t in (0, 1, 2, 3, 4, 5, 10, 13):
+for t in (0, 1, 3, 5, 10, 13):
     assert lib.bu_emul_etc1s_batch(t, ep.ctypes.data, rows.ctypes.data, None, None, 1, o.ctypes.data) == -1
 np.savez(%r, **res)
 print("clean")
 """
 
 
-def run_host_build(so, tmp_path, sets):
-    """sets: name -> (ep, rows, aep, arows) with aep / arows None for no alpha slice; run in a child process (an UBSan report aborts it)"""
+def run_host_build(so, tmp_path, sets, targets=TARGETS, sely=None):
+    """sets: name -> (ep, rows, aep, arows) with aep / arows None for no alpha slice; run in a child process (an UBSan report aborts it).
+    sely: name -> the second word of each block's selector entry, for the ETC1 target"""
     inp, outp = tmp_path / "in.npz", tmp_path / "out.npz"
     arrays = {}
     for k, (ep, rows, aep, arows) in sets.items():
         arrays[k + "/ep"], arrays[k + "/rows"] = ep, rows
         if aep is not None:
             arrays[k + "/aep"], arrays[k + "/arows"] = aep, arows
+        if sely is not None:
+            arrays[k + "/sely"] = sely[k]
     np.savez(inp, **arrays)
-    r = subprocess.run([sys.executable, "-c", _CHILD % (str(so), str(inp), TARGETS, str(outp))], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, "-c", _CHILD % (str(so), str(inp), targets, str(outp))], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0 and "clean" in r.stdout, r.stderr[-2000:]
     return np.load(outp)
 
@@ -208,6 +214,63 @@ def check(res, oracle, sets, names):
 @pytest.fixture(scope="module")
 def ubsan_so(tmp_path_factory):
     return _build(tmp_path_factory.mktemp("etc1s_emul"), ubsan=True)
+
+
+@pytest.fixture(scope="module")
+def plain_so(tmp_path_factory):
+    return _build(tmp_path_factory.mktemp("etc1s_emul_plain"), ubsan=False)
+
+
+@pytest.fixture(params=["plain", "ubsan"])
+def either_so(request, plain_so, ubsan_so):
+    return plain_so if request.param == "plain" else ubsan_so
+
+
+def check_base(so, tmp_path, oracle, sets):
+    """ETC1 and RGBA32 of the host build against the oracle's own, byte for byte.  A codebook entry per block: the selector entries are
+    the oracle's (selectors_from_rows: rows, then the ETC1 selector bytes), so ETC1 reads a real second word"""
+    entries = {k: oracle.selectors_from_rows(v[1].astype("<u4").view(np.uint8).reshape(-1, 4)) for k, v in sets.items()}
+    sely = {k: np.ascontiguousarray(e[:, 4:]).view("<u4").reshape(-1).astype(np.uint32) for k, e in entries.items()}
+    res = run_host_build(so, tmp_path, sets, targets=BASE, sely=sely)
+    for k, (ep, rows, aep, arows) in sets.items():
+        for c0 in range(0, ep.size, CHUNK):
+            sl = slice(c0, c0 + CHUNK)
+            n = ep[sl].size
+            idx = (np.arange(n, dtype=np.uint32) | (np.arange(n, dtype=np.uint32) << 16)).astype(np.uint32)
+            assert (entries[k][sl][:, :4] == rows[sl].astype("<u4").view(np.uint8).reshape(n, 4)).all()
+            want = {"etc1": oracle.etc1s_to_etc1(idx, ep[sl], entries[k][sl]).reshape(n, 8),
+                    "rgba": rgba_of(oracle, ep[sl], rows[sl], None if aep is None else aep[sl], None if arows is None else arows[sl])}
+            for name in BASE:
+                got = res[k + "/" + name][sl]
+                bad = np.nonzero((got != want[name]).any(1))[0]
+                assert bad.size == 0, "%s / %s: %d blocks differ, first %d: %s vs %s (ep %08x rows %08x)" % (
+                    k, name, bad.size, c0 + bad[0], got[bad[0]], want[name][bad[0]], ep[sl][bad[0]], rows[sl][bad[0]])
+
+
+def test_exhaustive_palettes_etc1_rgba32(oracle, either_so, tmp_path):
+    ep, rows = exhaustive_set()
+    check_base(either_so, tmp_path, oracle, {"exhaustive": (ep, rows, None, None)})
+
+
+def test_random_blocks_etc1_rgba32(oracle, either_so, tmp_path):
+    ep, rows, aep, arows = random_set(N_RANDOM, seed=41)
+    check_base(either_so, tmp_path, oracle, {"alpha": (ep, rows, aep, arows), "opaque": (ep[:CHUNK], rows[:CHUNK], None, None)})
+
+
+def test_index_split_and_check(either_so):
+    """bu_etc1s_index: the halves of both index words, and bad <=> some index the block reads lies outside its codebook"""
+    lib = ctypes.CDLL(str(either_so))
+    lib.bu_emul_etc1s_index.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    lib.bu_emul_etc1s_index.restype = None
+    out = np.zeros(5, dtype=np.uint32)
+    edge = (0, 1, 6, 7, 8, 0xFFFF)
+    for n_ep, n_sel in ((7, 9), (1, 1), (0, 0), (65536, 65536)):
+        for e in edge:
+            for s in edge:
+                for has_a, ae, as_ in [(0, 0xFFFF, 0xFFFF)] + [(1, x, y) for x in edge for y in edge]:
+                    lib.bu_emul_etc1s_index(e | s << 16, has_a, ae | as_ << 16, n_ep, n_sel, out.ctypes.data)
+                    bad = e >= n_ep or s >= n_sel or (has_a == 1 and (ae >= n_ep or as_ >= n_sel))
+                    assert out.tolist() == [e, s, ae if has_a else 0, as_ if has_a else 0, int(bad)], (n_ep, n_sel, e, s, has_a, ae, as_)
 
 
 def test_exhaustive_palettes_bc4_r11(oracle, ubsan_so, tmp_path):
