@@ -42,6 +42,18 @@ __device__ __forceinline__ uint4 bu_ld_stream(const uint4* p)
     const bu_v4u r = __builtin_nontemporal_load(reinterpret_cast<const bu_v4u*>(p));
     return make_uint4(r.x, r.y, r.z, r.w);
 }
+// The same load through a pointer to the GLOBAL address space.  The multi-run layouts rebuild a run's addresses from integers (the run record comes out of
+// LDS), and a load through such a pointer is a flat_load: a 64-bit vector address, counted on lgkmcnt as well as vmcnt, so that no counted wait is possible
+// while one is pending.  Every run lies in device memory (hipMalloc'ed or mapped host memory: global either way), so the load may say so.
+__device__ __forceinline__ uint4 bu_ld_stream_global(const uint4* p)
+{
+    typedef const bu_v4u __attribute__((address_space(1))) * bu_global_v4u;
+    const bu_v4u r = __builtin_nontemporal_load((bu_global_v4u)p);
+    return make_uint4(r.x, r.y, r.z, r.w);
+}
+// (the compiler's own stores below say "global" for the same reason: every output lies in device memory, and in the multi-run kernels nothing else says so)
+typedef bu_v4u __attribute__((address_space(1))) * bu_global_out_v4u;
+typedef bu_v2u __attribute__((address_space(1))) * bu_global_out_v2u;
 // Output stores.  BU_ST_MODE selects the cache policy (experiment knob).  A/B inside one run (tools/exp/ab.sh), 2^20 blocks:
 //   0 nontemporal (nt)            copy 7.15  BC7 10.93  ETC1 25.1  RGBA32 21.2 us
 //   1 plain                            7.07      12.70       25.9         23.1     (results linger dirty in L2)
@@ -63,9 +75,9 @@ __device__ __forceinline__ void bu_st_stream(uint4* p, const uint4 v)
     bu_v4u r;
     r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
 #if BU_ST_MODE == 0
-    __builtin_nontemporal_store(r, reinterpret_cast<bu_v4u*>(p));
+    __builtin_nontemporal_store(r, (bu_global_out_v4u)p);
 #elif BU_ST_MODE == 1
-    *reinterpret_cast<bu_v4u*>(p) = r;
+    *(bu_global_out_v4u)p = r;
 #else
     // hipcc does not model an asm store: the s_nop 1 keeps its next instruction from overwriting the data registers before
     // the store has read them (two wait states behind a store of more than 8 bytes on gfx940+)
@@ -79,9 +91,9 @@ __device__ __forceinline__ void bu_st_stream(uint2* p, const uint2 v)
     // 8-byte stores stay nontemporal: an sc1 store narrower than 16 bytes is one fabric write per lane
     // (ETC1S -> ETC1 at 2^18 blocks: 4.7 -> 6.2 us with sc1 nt)
 #if BU_ST_MODE == 1
-    *reinterpret_cast<bu_v2u*>(p) = r;
+    *(bu_global_out_v2u)p = r;
 #else
-    __builtin_nontemporal_store(r, reinterpret_cast<bu_v2u*>(p));
+    __builtin_nontemporal_store(r, (bu_global_out_v2u)p);
 #endif
 }
 
@@ -322,7 +334,10 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
                 }
                 r = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
                 // (the record comes back in vector registers -- an LDS read --, but every lane read the same one: made scalar here, so that the tile's addresses
-                //  are an SGPR base and a VGPR offset like the one-slice kernel's, not 64-bit vector arithmetic per load and store)
+                //  are a wave-uniform 64-bit base.  That is all it buys: every load and store still adds its lane offset to that base with 64-bit VECTOR arithmetic
+                //  (v_lshl_add_u64, then `off`) -- the SGPR-base + 32-bit-offset form of the one-slice kernels does not come out of it, a lane offset times 16 does not
+                //  provably fit 32 bits.  The pointers are rebuilt from integers, so the compiler no longer knows their address space either: the block loads say
+                //  "global" themselves (bu_ld_stream_global), the result stores are asm global stores in any case)
                 const BuRunDesc rv = R->run[r];
                 const BuRunDesc rd = {reinterpret_cast<const uint4*>(uni64(reinterpret_cast<uint64_t>(rv.in))), reinterpret_cast<void*>(uni64(reinterpret_cast<uint64_t>(rv.out))),
                                       uni64(rv.base), uni32(rv.n), uni32(rv.vshift)};
@@ -344,6 +359,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // MULTI: block l of the tile described by d, as an index inside d's run (strips: consecutive; rectangles: row l / 64, column l % 64 of the tile)
     auto run_idx = [&](const BuTileDesc& d, unsigned l) { return d.first + ((WHOLE || d.width) ? (l / BU_RECT_W) * d.width + (l % BU_RECT_W) : l); };
     auto blk_src = [&](unsigned t, unsigned l) { return MULTI ? tl.in + run_idx(tl, l) : in + gidx(t, l); };
+    auto ld_blk = [&](unsigned t, unsigned l) { return MULTI ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
     auto blk_valid = [&](unsigned t, unsigned l) {
         if constexpr (MULTI) return t < n_tiles && (WHOLE || l < tl.n);
         else return RECT ? t < n_tiles : (t < n_tiles && gidx(t, l) < n_blocks && in_tile(l));
@@ -372,7 +388,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     uint4 v[BU_BPT];
 #pragma unroll
     for (int j = 0; j < BU_BPT; j++)
-        v[j] = (RECT || blk_valid(tile, j * BU_WG + tid)) ? bu_ld_stream(blk_src(tile, j * BU_WG + tid)) : make_uint4(0, 0, 0, 0);  // (RECT: the grid is at most n_tiles)
+        v[j] = (RECT || blk_valid(tile, j * BU_WG + tid)) ? ld_blk(tile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);  // (RECT: the grid is at most n_tiles)
     if constexpr (!SPLIT) {
 #pragma unroll
         for (int k = 0; k < TVN; k++) {
@@ -395,8 +411,35 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     if constexpr (RUNS_IN_LDS) R = reinterpret_cast<const BuRunTable*>(s_runs);
     unsigned par = 0;
     unsigned next_of_loop = 0;
+    // STORES_LAST (the multi-run BC7 / ASTC kernels with PREFETCH): a tile's result stores are the LAST thing its iteration issues.  vmcnt counts loads and stores in issue order and
+    // the compiler does not count the asm stores of bu_st_stream, so whatever is waited for behind them -- the prefetched blocks `vn`, the drawn ticket -- also
+    // waits for their write-through acknowledgement with nothing of the wave's in flight.  Phase D therefore takes the results out of LDS, then consumes what is
+    // in flight (the next tile's sort keys out of `vn`, thread 0's next tile out of `my_draw`: they cross the loop edge in `key` / `drawn_tile`), then stores;
+    // nothing waits on those stores until the same point of the next tile.  BPT x 4 more live registers at that point.  ASTC takes it in the whole-tile layouts
+    // only: its 512 x 2 kernels are held to 64 VGPRs (__launch_bounds__(512, 8)), and its 256 x 4 strip kernel would go from 79 to 97 VGPRs -- four workgroups
+    // per CU where the launcher counts on five.  Every target whose results do not travel as one uint4 per block keeps the plain tail too.
+    // The ONE-SLICE kernels keep the plain tail as well, all of them: a lone atlas runs bu_uastc_sorted_kernel<BC7, 512, 2, prefetch, RECT> as one-tile workgroups, which
+    // have no next tile and pay for this order (results out of LDS first, keys of an empty `vn`) in front of their only stores: 8.41 -> 8.61 us per 2^20-block atlas.
+    // The multi-run kernels run as one-tile workgroups only between one tile per CU and one grid of tiles (bu_plan_multi_kernel).
+    constexpr bool STORES_LAST = PREFETCH && MULTI && (TARGET == BU_TGT_BC7 || (TARGET == BU_TGT_ASTC && WGS == 256 && WHOLE));
+    // STORES_LAST: sort key of block l of the tile described by d whose first word is x
+    auto key_of = [&](const BuTileDesc& d, unsigned l, uint32_t x) { return (WHOLE || l < d.n) ? (uint32_t)T.key_lut[bu_cost_row(TARGET)][x & 127u] : 31u; };
+    uint32_t next_key[STORES_LAST ? BU_BPT : 1];  // STORES_LAST: the keys of the tile about to be sorted, taken in phase D of the tile before it
+    uint32_t drawn_tile = 0;  // thread 0, STORES_LAST: tile_of_draw(my_draw), taken before the stores went out
+    if constexpr (STORES_LAST) {
+        if (tile < n_tiles) {
+#pragma unroll
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(td, j * BU_WG + tid, v[j].x);
+        }
+        if (ticket && tid == 0) drawn_tile = tile_of_draw(my_draw);
+        // Nothing of the prologue is still in flight here in practice (the table pieces were stored to LDS before the barrier above, the first tile's keys and the first
+        // draw have just been used) -- but every one of those uses sits behind a condition, and the compiler's wait-count bookkeeping is path-insensitive: it would carry
+        // "a load into these registers may be pending" into the loop and wait for vmcnt(0) at the first write to one of them in EVERY iteration, which lands a few
+        // instructions behind the previous tile's stores.  One full wait here, outside the loop, clears its books.  (vmcnt(0), the other counters untouched)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
     for (; tile < n_tiles; tile = next_of_loop, par ^= 1u) {
-        const unsigned tbase = tile * tile_blocks;
+        [[maybe_unused]] const unsigned tbase = tile * tile_blocks;
         // ---- A: sort key + rank within the key (counting sort, pass 1) ----
         // key = position of the block's mode in BU_COST_ORDER (runs are laid out heaviest code path first).
         // Rank within the key = one LDS atomic per block.  64 lanes adding to ONE counter serialise, though, and that is
@@ -407,8 +450,12 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         bool uniform = true;
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
-            const bool valid = WHOLE || (MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
-            key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
+            if constexpr (STORES_LAST) {
+                key[j] = next_key[j];
+            } else {
+                const bool valid = WHOLE || (MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
+                key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
+            }
             uniform = uniform && (__ballot(key[j] == (uint32_t)__builtin_amdgcn_readfirstlane(key[j])) == ~0ull) && has_block(key[j]);
         }
         if (uniform) {
@@ -421,7 +468,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) pos[j] = atomicAdd(&cnt[par][key[j]], 1u);  // lanes past the end hit the dummy counter 31: no exec-mask region, the atomics issue back to back
         }
-        if (ticket && tid == 0) s_next_tile[par] = tile_of_draw(my_draw);
+        if (ticket && tid == 0) s_next_tile[par] = STORES_LAST ? drawn_tile : tile_of_draw(my_draw);
         if (!tables_staged) {  // (key_lut is rewritten with the bytes it already holds)
 #pragma unroll
             for (int k = 0; k < TVN; k++) {
@@ -457,7 +504,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             desc_of(ntile, tl);
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) {
-                vn[j] = blk_valid(ntile, j * BU_WG + tid) ? bu_ld_stream(blk_src(ntile, j * BU_WG + tid)) : make_uint4(0, 0, 0, 0);
+                vn[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
             }
         }
         if (ticket && tid == 0 && ntile < n_tiles) my_draw = atomicAdd(my_counter, 1u);  // (for the tile after the next: needed one tile from now)
@@ -513,6 +560,35 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         }
         __syncthreads();  // (3) every result is in LDS
         // ---- D: results leave in original order ----
+        if constexpr (STORES_LAST) {
+            uint4 r[BU_BPT];
+            bool has[BU_BPT];
+            auto out_idx = [&](int j) { return run_idx(td, j * BU_WG + tid); };  // (inside the tile's slice)
+#pragma unroll
+            for (int j = 0; j < BU_BPT; j++) {
+                has[j] = has_block(key[j]);
+                if (has[j]) {
+                    r[j] = sblk[dest[j]];
+                    if ((r[j].x & 0xFFu) == 0u) {  // no valid block of these formats starts with a zero byte: word 3 is the status
+                        bu_report(status, td.base + out_idx(j), (int)r[j].w);
+                        r[j].w = 0;
+                    }
+                }
+            }
+            // everything this wave still has in flight is consumed HERE, in front of the stores (the asm stores clobber memory: the LDS reads of key_lut stay
+            // on this side of them, and so does the compiler's wait for `vn`)
+            // (on EVERY path, needed or not -- behind the last tile `vn` is zeros and the draw is stale: the compiler's wait-count bookkeeping is path-insensitive,
+            //  and a use under a condition would leave "may still be pending" standing, to be waited for at the next write to these registers: behind the stores)
+#pragma unroll
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(tl, j * BU_WG + tid, vn[j].x);
+            drawn_tile = tile_of_draw(my_draw);   // (every lane, with or without tickets: thread 0's is the one that counts, and only under tickets.  These few
+                                                  //  instructions and the key look-ups of a zero `vn` behind a workgroup's last tile are work done to steer the
+                                                  //  wait-count pass; tests/test_multi_kernel_address_space.py holds what they buy)
+            asm volatile("" : "+v"(drawn_tile));  // (plain arithmetic: pinned in front of the stores by hand)
+#pragma unroll
+            for (int j = 0; j < BU_BPT; j++)
+                if (has[j]) bu_st_stream(reinterpret_cast<uint4*>(td.out) + out_idx(j), r[j]);
+        } else {
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
             if (has_block(key[j])) {
@@ -552,6 +628,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
                 }
             }
         }
+        }
         if constexpr (PREFETCH) {
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) v[j] = vn[j];
@@ -560,7 +637,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             desc_of(ntile, tl);
             td = tl;
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? bu_ld_stream(blk_src(ntile, j * BU_WG + tid)) : make_uint4(0, 0, 0, 0);
+            for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
         }
         // no barrier here: the next tile's scatter into `sblk` sits behind its barrier (1), which every wave reaches only
         // after its reads of this tile's results have completed

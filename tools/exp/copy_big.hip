@@ -1,6 +1,7 @@
 // EXPERIMENT: how fast can ANY traversal copy 512 MiB -> 512 MiB (BASELINE config 5's bytes) on this box, and does the transcoder's traversal -- a persistent grid walking
 // 1024-block tiles, strips or 64 x 16-block rectangles at a 1024-block pitch, next tile's loads in flight -- cost bandwidth by itself?
-// hipcc --offload-arch=gfx950 -O3 -Wno-unused-result -o tools/exp/copy_big tools/exp/copy_big.hip
+// hipcc --offload-arch=gfx950 -O3 -Wno-unused-result -mllvm -amdgpu-atomic-optimizer-strategy=None -o tools/exp/copy_big tools/exp/copy_big.hip
+// (the library's flag: without it the ticket draw is wrapped in a wave reduction that waits for the atomic's return on the spot)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -161,6 +162,64 @@ __global__ void persist_ticket8(const uint4* __restrict__ in, uint4* __restrict_
         t = nt;
     }
 }
+// The library's tile loop, reduced to its memory instructions, to bound what the result stores cost the NEXT tile's load wait.  Stores are the library's `sc1 nt` asm
+// stores, which the compiler does not count: its wait for the prefetched tile (issued before them) is a vmcnt that also covers them.  `work` units of 64 x 16 clocks
+// of sleep stand for the transcode between the prefetch and the stores (0: a bare copy).
+// REORDER = false, the library's order: the prefetched tile and the drawn ticket are consumed at the TOP of the next iteration, right behind this tile's stores.
+// REORDER = true: they are consumed BEFORE this tile's stores go out; nothing waits on those stores until the next consumption point, a whole tile later.
+__device__ inline void st_sc1nt(uint4* p, uint4 v) { v4u t = {v.x, v.y, v.z, v.w}; asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(t) : "memory"); }
+__device__ inline void consume(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)::"memory"); }  // the value must be in its registers HERE
+template <int WGS, int RW, bool REORDER>
+__global__ void persist_ticket8_order(const uint4* __restrict__ in, uint4* __restrict__ out, unsigned n_tiles, unsigned* counters, unsigned work)
+{
+    constexpr int BPT = 1024 / WGS;
+    __shared__ unsigned s_t[2];
+    unsigned* const my = counters + (blockIdx.x & 7u) * 32u;
+    const unsigned c = blockIdx.x & 7u;
+    uint4 v[BPT], vn[BPT];
+    unsigned t = blockIdx.x;
+    unsigned draw = 0, par = 0;
+    if (threadIdx.x == 0) draw = atomicAdd(my, 1u);
+    if (t >= n_tiles) return;
+#pragma unroll
+    for (int j = 0; j < BPT; j++) v[j] = ldnt(in + tile_idx<RW>(t, j * WGS + threadIdx.x));
+    unsigned drawn_tile = 0;
+    if (REORDER) {
+#pragma unroll
+        for (int j = 0; j < BPT; j++) consume(v[j]);
+        if (threadIdx.x == 0) { drawn_tile = (gridDim.x / 8u + draw) * 8u + c; asm volatile("" : "+v"(drawn_tile)); }
+    }
+    for (;; par ^= 1u) {
+        if (!REORDER) {
+#pragma unroll
+            for (int j = 0; j < BPT; j++) consume(v[j]);  // (the sort keys of phase A)
+            if (threadIdx.x == 0) drawn_tile = (gridDim.x / 8u + draw) * 8u + c;
+        }
+        if (threadIdx.x == 0) s_t[par] = drawn_tile;
+        __syncthreads();
+        const unsigned nt = s_t[par];
+        if (nt >= n_tiles) {  // the last tile: nothing to prefetch
+            for (unsigned d = work; d; d--) __builtin_amdgcn_s_sleep(16);
+#pragma unroll
+            for (int j = 0; j < BPT; j++) st_sc1nt(out + tile_idx<RW>(t, j * WGS + threadIdx.x), v[j]);
+            break;
+        }
+#pragma unroll
+        for (int j = 0; j < BPT; j++) vn[j] = ldnt(in + tile_idx<RW>(nt, j * WGS + threadIdx.x));
+        if (threadIdx.x == 0) draw = atomicAdd(my, 1u);
+        for (unsigned d = work; d; d--) __builtin_amdgcn_s_sleep(16);
+        if (REORDER) {
+#pragma unroll
+            for (int j = 0; j < BPT; j++) consume(vn[j]);
+            if (threadIdx.x == 0) { drawn_tile = (gridDim.x / 8u + draw) * 8u + c; asm volatile("" : "+v"(drawn_tile)); }
+        }
+#pragma unroll
+        for (int j = 0; j < BPT; j++) st_sc1nt(out + tile_idx<RW>(t, j * WGS + threadIdx.x), v[j]);
+#pragma unroll
+        for (int j = 0; j < BPT; j++) v[j] = vn[j];
+        t = nt;
+    }
+}
 // semi-persistent: gridDim.x = n_tiles / K workgroups, each walks K tiles (prefetch) and exits; CONTIG: tiles K w .. K w + K - 1, else w, w + G, w + 2 G, ...
 template <int WGS, int RW, bool CONTIG>
 __global__ void semi(const uint4* __restrict__ in, uint4* __restrict__ out, unsigned n_tiles, unsigned K)
@@ -254,6 +313,26 @@ int main()
     printf("input: %s\n", (getenv("COPY_BIG_FILL") && getenv("COPY_BIG_FILL")[0] == 'c') ? "constant bytes" : "pseudo-random bytes");
     const unsigned tiles = (unsigned)(N / 1024);
     g_reps = (int)(((size_t)1 << 28) / N); if (g_reps < 8) g_reps = 8;
+    if (getenv("COPY_BIG_ONLY") && getenv("COPY_BIG_ONLY")[0] == 'o') {
+        // the store-order table alone (profiles/store_wait_behind_result_stores_copy_model_and_kernels.txt): rounds of one-pass copy / the existing ticketed copy / the library's order / the reordered
+        // loop, alternating inside one process, at four and five workgroups per CU, bare and with ~2.6, 4.3 and 6 us of stand-in work per tile (the last two make the walk latency-bound)
+        unsigned* ctr; hipMalloc(&ctr, 8 * 128);
+        auto ord = [&](auto kern, int per_cu, unsigned work) { return [=](const uint4* a, uint4* b) { hipMemsetAsync(ctr, 0, 8 * 128, 0); hipLaunchKernelGGL(kern, dim3(256 * per_cu), dim3(256), 0, 0, a, b, tiles, ctr, work); }; };
+        auto old8 = [&](int per_cu) { return [=](const uint4* a, uint4* b) { hipMemsetAsync(ctr, 0, 8 * 128, 0); hipLaunchKernelGGL((persist_ticket8<256, 64>), dim3(256 * per_cu), dim3(256), 0, 0, a, b, tiles, ctr); }; };
+        for (int round = 0; round < 3; round++) {
+            printf("-- round %d\n", round);
+            for (int per_cu : {4, 5}) {
+                char nm[96];
+                run("oneshot tile 256x4, 64-wide rectangles", [&](const uint4* a, uint4* b) { hipLaunchKernelGGL((oneshot_tile<256, 64>), dim3(tiles), dim3(256), 0, 0, a, b); });
+                snprintf(nm, sizeof nm, "%d/CU 8 tickets, builtin nt stores", per_cu); run(nm, old8(per_cu));
+                for (unsigned work : {0u, 6u, 10u, 14u}) {
+                    snprintf(nm, sizeof nm, "%d/CU asm stores, library order, work %u", per_cu, work); run(nm, ord(persist_ticket8_order<256, 64, false>, per_cu, work));
+                    snprintf(nm, sizeof nm, "%d/CU asm stores, REORDERED, work %u", per_cu, work); run(nm, ord(persist_ticket8_order<256, 64, true>, per_cu, work));
+                }
+            }
+        }
+        return 0;
+    }
     run("oneshot 256 x 4 plain", [&](const uint4* a, uint4* b) { hipLaunchKernelGGL((oneshot<4, false>), dim3(N / 1024), dim3(256), 0, 0, a, b, N); });
     run("oneshot 256 x 4 nt", [&](const uint4* a, uint4* b) { hipLaunchKernelGGL((oneshot<4, true>), dim3(N / 1024), dim3(256), 0, 0, a, b, N); });
     run("oneshot 512 x 2 nt", [&](const uint4* a, uint4* b) { hipLaunchKernelGGL((oneshot<2, true>), dim3(N / 1024), dim3(512), 0, 0, a, b, N); });
