@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     basislz_decode,
     crc16,
     etc1s_selector_from_rows,
+    read_file_query,
+    read_file_to,
     read_header,
     read_query,
     read_slice_descs,

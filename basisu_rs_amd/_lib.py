@@ -13,7 +13,7 @@ BC1_RGB, BC3_RGBA = 11, 12  # colour targets (BC1 drops A; BC3 = BC4 of A + BC1)
 BLOCK_BYTES = {ASTC: 16, BC7: 16, ETC1: 8, ETC2: 16, RGBA32: 64, BC4_R: 8, BC5_RG: 16, EAC_R11: 8, EAC_RG11: 16, BC1_RGB: 8, BC3_RGBA: 16}
 # bu_status
 OK, ERR_INVALID_MODE, ERR_INVALID_PATTERN, ERR_LENGTH, ERR_OUTPUT_SIZE, ERR_ARGUMENT, ERR_INDEX_RANGE, ERR_NO_DEVICE, ERR_HIP = range(9)
-ERR_UNSUPPORTED, ERR_BOUNDS = 17, 19
+ERR_DATA_CRC, ERR_ALPHA_SLICES, ERR_UNSUPPORTED, ERR_BOUNDS = 13, 16, 17, 19
 STATUS_WORD_CLEAR = 0xFFFFFFFFFFFFFFFF
 
 # every symbol include/basisu_hip.h declares (tests check the library exports all of them)
@@ -25,7 +25,7 @@ SYMBOLS = [
     "bu_uastc_transcode_device", "bu_uastc_transcode_batch_device", "bu_uastc_transcode_batch_in_flight", "bu_status_word_reset", "bu_status_word_decode", "bu_host_alloc", "bu_host_free",
     "bu_etc1s_selector_from_rows", "bu_etc1s_transcode_etc1_device", "bu_etc1s_decode_rgba_device",
     "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode",
-    "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_basislz_decode",
+    "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_read_file_query", "bu_read_file_to", "bu_basislz_decode",
     "bu_basis_write_uastc",
     "bu_comm_unique_id", "bu_comm_create", "bu_comm_destroy", "bu_comm_query", "bu_allgather_inplace",
     "bu_ipc_export", "bu_ipc_open", "bu_ipc_close", "bu_allgather_peer", "bu_array_transcode_sharded",
@@ -157,6 +157,10 @@ def load():
     lib.bu_read_query.restype = c.c_int
     lib.bu_read_to.argtypes = [vp, c.c_int, vp, sz, c.POINTER(BasisHeader), c.POINTER(ImageDesc), sz, szp, vp, sz]
     lib.bu_read_to.restype = c.c_int
+    lib.bu_read_file_query.argtypes = lib.bu_read_query.argtypes  # (the first argument is a bu_target)
+    lib.bu_read_file_query.restype = c.c_int
+    lib.bu_read_file_to.argtypes = lib.bu_read_to.argtypes
+    lib.bu_read_file_to.restype = c.c_int
     lib.bu_basislz_decode.argtypes = [vp, sz, u32, vp, vp, vp]
     lib.bu_basislz_decode.restype = c.c_int
     lib.bu_basis_write_uastc.argtypes = [c.POINTER(SliceDesc), c.POINTER(vp), szp, sz, c.c_uint16, c.c_uint8, vp, sz, szp]

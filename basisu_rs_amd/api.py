@@ -356,14 +356,24 @@ def read_query(target, buf):
     return n.value, nb.value
 
 
-def _read_to(target, buf, ctx=None, out=None):
-    """`out`: optional caller buffer of at least read_query()[1] bytes; one from Context.host_alloc() is written by the
-    kernels directly over PCIe (no device output buffer, no download)."""
+def read_file_query(fmt, buf):
+    """(number of images, total output bytes) of read_file_to(fmt, buf) (bu_read_file_query; host only)"""
     lib = _lib.load()
     a = _as_u8(buf)
     n, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check_host(lib.bu_read_file_query(int(fmt), a.ctypes.data, a.size, ctypes.byref(n), ctypes.byref(nb)))
+    return n.value, nb.value
+
+
+def _read_to(target, buf, ctx=None, out=None, by_format=False):
+    """`out`: optional caller buffer of at least read_query()[1] bytes; one from Context.host_alloc() is written by the
+    kernels directly over PCIe (no device output buffer, no download).  by_format: `target` is a bu_target (bu_read_file_to)."""
+    lib = _lib.load()
+    query, read = (lib.bu_read_file_query, lib.bu_read_file_to) if by_format else (lib.bu_read_query, lib.bu_read_to)
+    a = _as_u8(buf)
+    n, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
     if out is None:
-        _check_host(lib.bu_read_query(target, a.ctypes.data, a.size, ctypes.byref(n), ctypes.byref(nb)))
+        _check_host(query(target, a.ctypes.data, a.size, ctypes.byref(n), ctypes.byref(nb)))
         out = np.empty(max(nb.value, 1), dtype=np.uint8)
         max_images = n.value
     else:  # the caller sized the buffer (read_query): no second pass over the payload CRC, one image per slice at most
@@ -373,7 +383,7 @@ def _read_to(target, buf, ctx=None, out=None):
     c = ctx or default_context()
     imgs = (_lib.ImageDesc * max(max_images, 1))()
     h = _lib.BasisHeader()
-    st = lib.bu_read_to(c.handle, target, a.ctypes.data, a.size, ctypes.byref(h), imgs, max_images, ctypes.byref(n), out.ctypes.data, out.size)
+    st = read(c.handle, target, a.ctypes.data, a.size, ctypes.byref(h), imgs, max_images, ctypes.byref(n), out.ctypes.data, out.size)
     c._check(st)
     return h, [Image(im.w, im.h, im.stride, out[im.offset:im.offset + im.size]) for im in imgs[: n.value]]
 
@@ -424,6 +434,13 @@ def read_to_bc1(buf, ctx=None, out=None):  # UASTC files only: BC1 of RGB (A dro
 
 def read_to_bc3(buf, ctx=None, out=None):  # UASTC files only: BC3 (BC4 of A, BC1 of RGB)
     return _read_to(_lib.READ_BC3, buf, ctx, out)[1]
+
+
+def read_file_to(fmt, buf, ctx=None, out=None):
+    """A .basis file of either kind to the block format `fmt` (a TargetTextureFormat or bu_target number; bu_read_file_to) -> [Image].
+    A UASTC file takes every format; an ETC1S file takes Etc1, RGBA32 (4) and Bc4R, Bc5Rg, EacR11, EacRg11, Bc1Rgb, Bc3Rgba, one image per
+    colour / alpha slice pair for all but Etc1.  `out` as for the read_to_* functions, sized by read_file_query."""
+    return _read_to(int(fmt), buf, ctx, out, by_format=True)[1]
 
 
 def basislz_decode(buf, slice_index=None):

@@ -1201,13 +1201,16 @@ struct BuFilePlan {
     std::vector<bu_image> images;       // one per output image
     std::vector<size_t> first_slice;    // slice feeding image i (its colour slice for RGBA+alpha)
     size_t out_bytes = 0;
-    bool etc1s = false, alpha_pairs = false;
+    bool etc1s = false, alpha_pairs = false;  // alpha_pairs: an image is a colour / alpha slice pair (ETC1S with alpha: RGBA32 and the six targets)
+    bool etc1s_six = false;                   // an ETC1S file read to BC4 .. BC3 (bu_read_file_to): block-linear images, the image list of RGBA32
 };
 
 // everything of read_to_* that needs no block work: checks in the reference's order, image geometry
 // check_data_crc = false: the caller verifies the payload CRC itself (bu_read_to overlaps it with the upload) and gives
 // a CRC failure precedence over any later error, as the reference's order of checks would
-inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t len, BuFilePlan& p, bool check_data_crc = true)
+// etc1s_six = true (bu_read_file_query / bu_read_file_to): an ETC1S file takes BU_READ_BC4 .. BU_READ_BC3 too -- the image list and the
+// alpha-slice checks of BU_READ_RGBA, block-linear images of the target's block size; nothing else changes
+inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t len, BuFilePlan& p, bool check_data_crc = true, bool etc1s_six = false)
 {
     if (!file) return BU_ERR_ARGUMENT;
     if ((int)target < 0 || (int)target > (int)BU_READ_BC3 || (int)target == 10) return BU_ERR_ARGUMENT;  // (10 names no read target)
@@ -1219,10 +1222,11 @@ inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t
     if (p.h.tex_format > 1) return BU_ERR_TEX_FORMAT;
     p.etc1s = p.h.tex_format == 0;
     const bool has_alpha = (p.h.flags & 4) != 0;
-    if (p.etc1s && (int)target >= (int)BU_READ_BC4) return BU_ERR_ARGUMENT;  // (ETC1S to the channel and colour targets: not offered)
-    if (p.etc1s && !(target == BU_READ_RGBA || target == BU_READ_ETC1)) return BU_ERR_UNSUPPORTED;
+    p.etc1s_six = p.etc1s && etc1s_six && (int)target >= (int)BU_READ_BC4;
+    if (p.etc1s && (int)target >= (int)BU_READ_BC4 && !p.etc1s_six) return BU_ERR_ARGUMENT;  // (ETC1S to the channel and colour targets: bu_read_file_to)
+    if (p.etc1s && !(target == BU_READ_RGBA || target == BU_READ_ETC1 || p.etc1s_six)) return BU_ERR_UNSUPPORTED;
     if (p.etc1s && has_alpha && (p.slices.size() % 2) != 0) return BU_ERR_ALPHA_SLICES;
-    p.alpha_pairs = p.etc1s && has_alpha && target == BU_READ_RGBA;
+    p.alpha_pairs = p.etc1s && has_alpha && (target == BU_READ_RGBA || p.etc1s_six);
     for (size_t i = 0; i < p.slices.size(); i++) {
         const bu_slice_desc& s = p.slices[i];
         if (!in_file(len, s.file_ofs, s.file_size)) return BU_ERR_BOUNDS;
@@ -1233,14 +1237,15 @@ inline bu_status bu_plan_file(bu_read_target target, const uint8_t* file, size_t
             if (a.num_blocks_x != s.num_blocks_x || a.num_blocks_y != s.num_blocks_y) return BU_ERR_ALPHA_SLICES;
         }
         const size_t nblk = (size_t)s.num_blocks_x * s.num_blocks_y, nb16 = s.file_size / 16;
+        const bool eight = target == BU_READ_ETC1 || target == BU_READ_BC4 || target == BU_READ_EAC_R11 || target == BU_READ_BC1;  // 8-byte blocks
         bu_image im = {s.orig_width, s.orig_height, 0, 0, p.out_bytes, 0};
         if (p.etc1s) {
             if (target == BU_READ_RGBA) {
                 im.size = nblk * 64;
                 im.stride = 16u * s.orig_width;  // basis.rs:46,64 x4 (lib.rs:75): reference quirk, rows are 16*nbx apart
-            } else {
-                im.size = nblk * 8;
-                im.stride = 8u * s.num_blocks_x;
+            } else {  // ETC1 and the six targets: block-linear
+                im.size = nblk * (eight ? 8 : 16);
+                im.stride = (eight ? 8u : 16u) * s.num_blocks_x;
             }
         } else {
             if (target != BU_READ_UASTC && s.file_size % 16) return BU_ERR_LENGTH;  // uastc.rs:54-59

@@ -50,10 +50,22 @@ static bu_target bu_read_block_target(bu_read_target target)
     }
 }
 
-static bu_status bu_read_query_impl(bu_read_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes)
+// the read target whose block target `target` is (bu_read_block_target inverted); false: `target` is no bu_target
+static bool bu_block_read_target(bu_target target, bu_read_target* out)
+{
+    for (int t = (int)BU_READ_RGBA; t <= (int)BU_READ_BC3; t++)
+        if (t != (int)BU_READ_UASTC && t != 10 && bu_read_block_target((bu_read_target)t) == target) {
+            *out = (bu_read_target)t;
+            return true;
+        }
+    return false;
+}
+
+// etc1s_six: the call is bu_read_file_query (bu_plan_file)
+static bu_status bu_read_query_impl(bu_read_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes, bool etc1s_six = false)
 {
     BuFilePlan p;
-    bu_status st = bu_plan_file(target, file, len, p);
+    bu_status st = bu_plan_file(target, file, len, p, true, etc1s_six);
     if (st) return st;
     if (n_images) *n_images = p.images.size();
     if (out_bytes) *out_bytes = p.out_bytes;
@@ -85,13 +97,30 @@ static bu_status bu_basislz_decode_impl(const uint8_t* file, size_t len, uint32_
     return st;
 }
 
-// The whole-file ETC1S kernel (bu_etc1s_kernels.hpp) over the 64-block units [u0, u1) of the slices d_descs describes, on the context
-// stream: RGBA32 or ETC1, both codebooks of n_cb entries.  The caller asks hipGetLastError.
-static void bu_etc1s_file_launch(bu_context* ctx, bool rgba, unsigned grid, const uint32_t* d_idx, const BuEtc1sSlice* d_descs, uint32_t n_slices,
+// The whole-file ETC1S kernel (bu_etc1s_kernels.hpp) of a slot (bu_etc1s_slot's numbering: 0 ETC1, 1 RGBA32, 2.. the six targets) over
+// the 64-block units [u0, u1) of the slices d_descs describes, on the context stream; both codebooks of n_cb entries.  The caller
+// asks hipGetLastError.
+static void bu_etc1s_file_launch(bu_context* ctx, unsigned slot, unsigned grid, const uint32_t* d_idx, const BuEtc1sSlice* d_descs, uint32_t n_slices,
                                  uint32_t u0, uint32_t u1, const uint32_t* d_ep, const uint2* d_sel, uint32_t n_cb, uint8_t* d_out, uint64_t* d_status)
 {
-    hipLaunchKernelGGL(rgba ? bu_etc1s_file_kernel<true> : bu_etc1s_file_kernel<false>, dim3(grid), dim3(BU_WG), 0, ctx->stream, d_idx, d_descs, n_slices,
-                       u0, u1, d_ep, n_cb, d_sel, n_cb, d_out, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+    typedef void (*Fn)(const uint32_t*, const BuEtc1sSlice*, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t, const uint2*, uint32_t, uint8_t*,
+                       unsigned long long*, const BuTablesAll*);
+    static const Fn kernels[8] = {&bu_etc1s_file_kernel<false>,
+                                  &bu_etc1s_file_kernel<true>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_BC4>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_BC5>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_R11>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_RG11>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_BC1>,
+                                  &bu_etc1s_file_target_kernel<BU_TGT_BC3>};
+    hipLaunchKernelGGL(kernels[slot], dim3(grid), dim3(BU_WG), 0, ctx->stream, d_idx, d_descs, n_slices, u0, u1, d_ep, n_cb, d_sel, n_cb, d_out,
+                       reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+}
+
+// the slot of an ETC1S file's kernel: the plan's block target for the six (bu_read_file_to), else RGBA32 or ETC1
+static unsigned bu_etc1s_file_slot(const BuFilePlan& p, bu_read_target target)
+{
+    return p.etc1s_six ? bu_etc1s_target_slot(bu_read_block_target(target)) : target == BU_READ_RGBA ? 1u : 0u;
 }
 
 // ---- streamed ETC1S front door -------------------------------------------------------------------------------------------------
@@ -154,7 +183,7 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
         d.n_blocks = (uint32_t)nblk;
         d.nbx = sl.num_blocks_x;
         d.idx_ofs = (uint32_t)in_off[k];
-        d.aidx_ofs = (p.alpha_pairs && target == BU_READ_RGBA) ? (uint32_t)ain_off[k] : 0xFFFFFFFFu;
+        d.aidx_ofs = p.alpha_pairs ? (uint32_t)ain_off[k] : 0xFFFFFFFFu;
         d.image = (uint32_t)k;
         d.out_ofs = p.images[k].offset;
         descs.push_back(d);
@@ -276,7 +305,7 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     const uint32_t n_cb0 = (uint32_t)n_cb;
     auto launch = [&](uint32_t u0, uint32_t u1) -> bu_status {
         const unsigned grid = bu_grid_for((size_t)(u1 - u0) * 64, ctx->cu_count);
-        bu_etc1s_file_launch(ctx, target == BU_READ_RGBA, grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(descs.size() - 1), u0, u1,
+        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(descs.size() - 1), u0, u1,
                              reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
         BU_HIP(ctx, hipGetLastError());
         return BU_OK;
@@ -494,8 +523,9 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     return BU_OK;
 }
 
+// etc1s_six: the call is bu_read_file_to (bu_plan_file)
 static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, bu_basis_header* header_out, bu_image* images,
-                                size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes)
+                                size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes, bool etc1s_six = false)
 {
     if (!ctx || !out) return BU_ERR_ARGUMENT;
     const bool trace = getenv("BU_TRACE") != nullptr;
@@ -535,7 +565,7 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
         }
         return s;
     };
-    bu_status st = bu_plan_file(target, file, len, p, !crc_deferred);
+    bu_status st = bu_plan_file(target, file, len, p, !crc_deferred, etc1s_six);
     lap("plan (parse + CRCs)");
     if (st) return settle(st);
     const auto rest = [&]() -> bu_status {
@@ -656,7 +686,7 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
             d.n_blocks = (uint32_t)nblk;
             d.nbx = sl.num_blocks_x;
             d.idx_ofs = (uint32_t)(in_off[k] / 4);
-            d.aidx_ofs = (p.alpha_pairs && target == BU_READ_RGBA) ? (uint32_t)(ain_off[k] / 4) : 0xFFFFFFFFu;
+            d.aidx_ofs = p.alpha_pairs ? (uint32_t)(ain_off[k] / 4) : 0xFFFFFFFFu;
             d.image = (uint32_t)k;
             d.out_ofs = p.images[k].offset;
             descs.push_back(d);
@@ -693,7 +723,7 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
             const uint32_t n_cb0 = (uint32_t)lz.endpoints.size();
             const unsigned grid = bu_grid_for((size_t)n_units * 64, ctx->cu_count);
             const BuEtc1sSlice* d_descs = reinterpret_cast<const BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
-            bu_etc1s_file_launch(ctx, target == BU_READ_RGBA, grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(descs.size() - 1), 0u, n_units,
+            bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(descs.size() - 1), 0u, n_units,
                                  reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
             BU_HIP(ctx, hipGetLastError());
         }
@@ -851,6 +881,21 @@ bu_status bu_read_to(bu_context* ctx, bu_read_target target, const uint8_t* file
                      size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes)
 {
     BU_GUARDED(bu_read_to_impl(ctx, target, file, len, header_out, images, max_images, n_images, out, out_bytes))
+}
+// The file calls keyed by block format: a UASTC file, and ETC1 / RGBA32 of an ETC1S file, are bu_read_to's with the read target whose
+// block target this is; the six targets of an ETC1S file are planned with the flag.
+bu_status bu_read_file_query(bu_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes)
+{
+    bu_read_target rt;
+    if (!bu_block_read_target(target, &rt)) return BU_ERR_ARGUMENT;
+    BU_GUARDED(bu_read_query_impl(rt, file, len, n_images, out_bytes, true))
+}
+bu_status bu_read_file_to(bu_context* ctx, bu_target target, const uint8_t* file, size_t len, bu_basis_header* header_out, bu_image* images,
+                          size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes)
+{
+    bu_read_target rt;
+    if (!bu_block_read_target(target, &rt)) return BU_ERR_ARGUMENT;
+    BU_GUARDED(bu_read_to_impl(ctx, rt, file, len, header_out, images, max_images, n_images, out, out_bytes, true))
 }
 #undef BU_GUARDED
 

@@ -258,17 +258,7 @@ __global__ __launch_bounds__(STAGED ? 1024 : BU_WG) void bu_etc1s_target_kernel(
 // The host concatenates the per-slice index arrays (each padded to a multiple of 64 words) and describes the slices in a
 // small table; a wave owns one 64-block unit, finds its slice by a scalar binary search over the units' prefix and then
 // does exactly what the per-slice kernels do.  One status word per image, as the sequential drivers report.
-struct BuEtc1sSlice {
-    uint32_t unit0;     // first 64-block unit of this slice (the table ends with a sentinel holding the total)
-    uint32_t n_blocks;  // nbx * nby
-    uint32_t nbx;       // blocks per row (RGBA addressing)
-    uint32_t idx_ofs;   // colour indices, in words from the start of the staged index buffer
-    uint32_t aidx_ofs;  // alpha indices (RGBA with alpha pairs), 0xFFFFFFFF = none
-    uint32_t image;     // status word / image number
-    uint64_t out_ofs;   // byte offset of the image in the output buffer
-};
-static_assert(sizeof(BuEtc1sSlice) == 32, "descriptor layout is shared with the host code");
-
+// (BuEtc1sSlice, the table's entry, and bu_etc1s_unit_slice, the search, are bu_etc1s_targets.hpp's: the CPU tests compile them too.)
 template <bool RGBA>
 __global__ __launch_bounds__(BU_WG) void bu_etc1s_file_kernel(const uint32_t* __restrict__ idx, const BuEtc1sSlice* __restrict__ slices, uint32_t n_slices,
                                                               uint32_t unit_begin, uint32_t n_units, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
@@ -303,6 +293,45 @@ __global__ __launch_bounds__(BU_WG) void bu_etc1s_file_kernel(const uint32_t* __
             bu_etc1s_rgba_lane(cb, pal_lut, bu_etc1s_index(ix, has_a, ax, n_ep, n_sel), has_a, status + sd.image, i, sd.nbx,
                                reinterpret_cast<uint4*>(out + sd.out_ofs));
         }
+    }
+}
+
+// The six targets of bu_etc1s_targets.hpp over a whole file (bu_read_file_to): the structure of bu_etc1s_file_kernel<true> -- a wave
+// per 64-block unit, the palette table in LDS, codebooks gathered through the L2 -- with bu_etc1s_target_kernel's block code and ONE
+// result store per lane at out + out_ofs: a wave writes 512 B (8-byte targets) or 1 KiB contiguous.  The unit number is made scalar
+// first, so the search of bu_etc1s_unit_slice and the descriptor are scalar loads.  A slice with aidx_ofs set has an alpha slice
+// (A = 255 without one); its indices are checked whether TARGET reads A or not, as bu_etc1s_transcode does.
+template <int TARGET>
+__global__ __launch_bounds__(BU_WG) void bu_etc1s_file_target_kernel(const uint32_t* __restrict__ idx, const BuEtc1sSlice* __restrict__ slices,
+                                                                     uint32_t n_slices, uint32_t unit_begin, uint32_t n_units,
+                                                                     const uint32_t* __restrict__ endpoints, uint32_t n_ep,
+                                                                     const uint2* __restrict__ selectors, uint32_t n_sel, uint8_t* __restrict__ out,
+                                                                     unsigned long long* status, const BuTablesAll* __restrict__ tables)
+{
+    __shared__ uint32_t pal_lut[256];
+    pal_lut[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
+    static_assert(BU_WG == 256, "one palette word per thread");
+    __syncthreads();
+    const BuEtc1sBooks<false> cb = {nullptr, nullptr, endpoints, selectors};
+    const BuTables& T = tables->t;  // (R11 / RG11: the EAC tables, read through the scalar cache in the table search)
+    const uint32_t lane = threadIdx.x & 63u, wpg = BU_WG / 64;
+    for (uint32_t u = unit_begin + blockIdx.x * wpg + (threadIdx.x >> 6); u < n_units; u += gridDim.x * wpg) {
+        const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)u);
+        const BuEtc1sSlice sd = slices[bu_etc1s_unit_slice(slices, n_slices, unit)];
+        const uint32_t i = (unit - sd.unit0) * 64u + lane;
+        if (i >= sd.n_blocks) continue;
+        const bool has_a = sd.aidx_ofs != 0xFFFFFFFFu;
+        const uint32_t ix = __builtin_nontemporal_load(idx + sd.idx_ofs + i);
+        const uint32_t ax = has_a ? __builtin_nontemporal_load(idx + sd.aidx_ofs + i) : 0u;
+        const BuEtc1sIndex k = bu_etc1s_index(ix, has_a, ax, n_ep, n_sel);
+        uint32_t o[4];
+        if (bu_etc1s_good(k, status + sd.image, i, o)) {
+            uint32_t pr, pg, pb, pa, rows, arows;
+            bu_etc1s_fetch(cb, pal_lut, k, has_a, pr, pg, pb, pa, rows, arows);
+            bu_etc1s_target_block<TARGET>(T, pr, pg, pb, rows, has_a, pa, arows, o);
+        }
+        if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out + sd.out_ofs) + i, make_uint2(o[0], o[1]));
+        else bu_st_stream(reinterpret_cast<uint4*>(out + sd.out_ofs) + i, make_uint4(o[0], o[1], o[2], o[3]));
     }
 }
 

@@ -395,3 +395,36 @@ BU_DEV void bu_etc1s_block_rgba(uint32_t pr, uint32_t pg, uint32_t pb, uint32_t 
         }
     }
 }
+
+// ---- the slice table of the whole-file kernels (bu_etc1s_kernels.hpp) -------------------------------------------------------------
+// The host concatenates the per-slice index arrays (each padded to a multiple of 64 words) and describes the slices in this table; a
+// wave owns one 64-block unit and finds its slice by a binary search over the units' prefix.  Slices without blocks get no entry, so
+// consecutive entries never share a unit0.  (In the unnamed namespace of the kernels that take it.)
+namespace {
+
+struct BuEtc1sSlice {
+    uint32_t unit0;     // first 64-block unit of this slice (the table ends with a sentinel holding the total)
+    uint32_t n_blocks;  // nbx * nby
+    uint32_t nbx;       // blocks per row (RGBA addressing)
+    uint32_t idx_ofs;   // colour indices, in words from the start of the staged index buffer
+    uint32_t aidx_ofs;  // alpha indices (alpha pairs: RGBA32 and the six targets), 0xFFFFFFFF = none
+    uint32_t image;     // status word / image number
+    uint64_t out_ofs;   // byte offset of the image in the output buffer
+};
+static_assert(sizeof(BuEtc1sSlice) == 32, "descriptor layout is shared with the host code");
+
+// The slice that holds `unit`: the largest s < n_slices with slices[s].unit0 <= unit (n_slices >= 1, slices[0].unit0 == 0).  Lane
+// (unit - unit0) * 64 + lane of that slice is a block of it when it lies below n_blocks: the last unit of a slice may be part empty.
+// On the device `unit` is wave-uniform and the table is read through the scalar cache.
+BU_DEV uint32_t bu_etc1s_unit_slice(const BuEtc1sSlice* slices, uint32_t n_slices, uint32_t unit)
+{
+    uint32_t lo = 0, hi = n_slices;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (slices[mid].unit0 <= unit) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+}  // namespace

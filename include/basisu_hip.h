@@ -356,14 +356,14 @@ typedef enum bu_read_target {
     BU_READ_UASTC = 3, /* read_to_uastc basis.rs:175 */
     BU_READ_ASTC = 4, /* read_to_astc  basis.rs:204 */
     BU_READ_BC7 = 5,  /* read_to_bc7   basis.rs:233 */
-    /* UASTC files only (BU_TARGET_BC4_R .. BU_TARGET_EAC_RG11 per slice); an ETC1S file returns BU_ERR_ARGUMENT -- its slices take
-     * bu_basislz_decode, then bu_etc1s_transcode */
+    /* UASTC files only (BU_TARGET_BC4_R .. BU_TARGET_EAC_RG11 per slice); an ETC1S file returns BU_ERR_ARGUMENT -- bu_read_file_to
+     * reads it to these formats (or, slice by slice: bu_basislz_decode, then bu_etc1s_transcode) */
     BU_READ_BC4 = 6,
     BU_READ_BC5 = 7,
     BU_READ_EAC_R11 = 8,
     BU_READ_EAC_RG11 = 9,
-    /* UASTC files only (BU_TARGET_BC1_RGB / BU_TARGET_BC3_RGBA per slice); an ETC1S file returns BU_ERR_ARGUMENT (its slices: bu_basislz_decode,
-     * then bu_etc1s_transcode); 10 names no read target */
+    /* UASTC files only (BU_TARGET_BC1_RGB / BU_TARGET_BC3_RGBA per slice); an ETC1S file returns BU_ERR_ARGUMENT (bu_read_file_to reads it
+     * to these formats; slice by slice: bu_basislz_decode, then bu_etc1s_transcode); 10 names no read target */
     BU_READ_BC1 = 11,
     BU_READ_BC3 = 12
 } bu_read_target;
@@ -384,6 +384,24 @@ bu_status bu_read_query(bu_read_target target, const uint8_t* file, size_t len, 
  * On an error return the contents of `out` are undefined (parts of it may already have been written). */
 bu_status bu_read_to(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, bu_basis_header* header_out,
                      bu_image* images, size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes);
+/* The whole-file call keyed by block format: every parameter and the error-return contract are bu_read_query's / bu_read_to's.
+ * A target that is no bu_target returns BU_ERR_ARGUMENT before the file is looked at; then the checks of bu_read_to in its order
+ * (header, payload CRC, slice descriptors, tex_format), and only then the kind of file:
+ *   UASTC file, any bu_target        bu_read_to with the read target of that block format: same status, images and bytes
+ *   ETC1S file, ETC1 / RGBA32        bu_read_to(BU_READ_ETC1 / BU_READ_RGBA): one image per slice for ETC1, the RGBA stride quirk
+ *   ETC1S file, ASTC / BC7 / ETC2    BU_ERR_UNSUPPORTED
+ *   ETC1S file, BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB, BC3_RGBA
+ *     the image list of BU_READ_RGBA on the same file: one image per colour / alpha slice pair when the header has HasAlphaSlices
+ *     (BU_ERR_ALPHA_SLICES for an odd slice count, a second slice without the alpha flag or unequal block grids), else one per slice;
+ *     w, h = the colour slice's orig_width / orig_height, stride = bu_target_block_bytes(target) * num_blocks_x,
+ *     size = num_blocks_x * num_blocks_y * bu_target_block_bytes(target), block-linear.  Block i of image k is bu_etc1s_transcode's
+ *     block i for the pair's colour and alpha indices and the file's codebooks: A = the alpha slice's
+ *     value, or 255 in a file without alpha slices.  In a file with alpha slices the alpha indices are decoded and validated whether
+ *     the target reads A or not, so the image list and the errors do not depend on the target; a bad slice or index is reported as
+ *     bu_read_to(BU_READ_RGBA) reports it for the same file. */
+bu_status bu_read_file_query(bu_target target, const uint8_t* file, size_t len, size_t* n_images, size_t* out_bytes);
+bu_status bu_read_file_to(bu_context* ctx, bu_target target, const uint8_t* file, size_t len, bu_basis_header* header_out,
+                          bu_image* images, size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes);
 /* Host-only BasisLZ decode of an ETC1S file (basis_lz/mod.rs:64-95, 188-458): the two codebooks in the layouts
  * the bu_etc1s_* entry points take, and the per-block indices of slice `slice_index`.  Any pointer may be NULL. */
 bu_status bu_basislz_decode(const uint8_t* file, size_t len, uint32_t slice_index, uint32_t* endpoints_out,

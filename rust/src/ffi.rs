@@ -170,6 +170,9 @@ extern "C" {
     pub fn bu_read_query(target: c_int, file: *const u8, len: usize, n_images: *mut usize, out_bytes: *mut usize) -> c_int;
     pub fn bu_read_to(ctx: *mut bu_context, target: c_int, file: *const u8, len: usize, header_out: *mut bu_basis_header,
                       images: *mut bu_image, max_images: usize, n_images: *mut usize, out: *mut u8, out_bytes: usize) -> c_int;
+    pub fn bu_read_file_query(target: c_int, file: *const u8, len: usize, n_images: *mut usize, out_bytes: *mut usize) -> c_int;
+    pub fn bu_read_file_to(ctx: *mut bu_context, target: c_int, file: *const u8, len: usize, header_out: *mut bu_basis_header,
+                           images: *mut bu_image, max_images: usize, n_images: *mut usize, out: *mut u8, out_bytes: usize) -> c_int;
     // multi-GPU: shards of one texture array
     pub fn bu_comm_unique_id(id: *mut u8) -> c_int;
     pub fn bu_comm_create(ctx: *mut bu_context, world: c_int, rank: c_int, id: *const u8, out_comm: *mut *mut bu_comm) -> c_int;

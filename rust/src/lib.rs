@@ -81,14 +81,22 @@ fn check(ctx: *mut ffi::bu_context, st: c_int) -> Result<()> {
 }
 
 fn read_to(target: c_int, buf: &[u8]) -> Result<(Header, Vec<Image<u8>>)> {
+    read_with(ffi::bu_read_query, ffi::bu_read_to, target, buf)
+}
+
+type QueryFn = unsafe extern "C" fn(c_int, *const u8, usize, *mut usize, *mut usize) -> c_int;
+type ReadFn = unsafe extern "C" fn(*mut ffi::bu_context, c_int, *const u8, usize, *mut Header, *mut ffi::bu_image, usize, *mut usize, *mut u8, usize) -> c_int;
+
+/// the query / read pair of the read targets (bu_read_query, bu_read_to) or of the block formats (bu_read_file_query, bu_read_file_to)
+fn read_with(query: QueryFn, read: ReadFn, target: c_int, buf: &[u8]) -> Result<(Header, Vec<Image<u8>>)> {
     let ctx = context()?;
     let (mut n_images, mut out_bytes) = (0usize, 0usize);
-    check(ctx, unsafe { ffi::bu_read_query(target, buf.as_ptr(), buf.len(), &mut n_images, &mut out_bytes) })?;
+    check(ctx, unsafe { query(target, buf.as_ptr(), buf.len(), &mut n_images, &mut out_bytes) })?;
     let mut out = vec![0u8; out_bytes.max(1)];
     let mut images = vec![ffi::bu_image::default(); n_images.max(1)];
     let mut header = Header::default();
     let st = unsafe {
-        ffi::bu_read_to(ctx, target, buf.as_ptr(), buf.len(), &mut header, images.as_mut_ptr(), n_images, &mut n_images, out.as_mut_ptr(), out.len())
+        read(ctx, target, buf.as_ptr(), buf.len(), &mut header, images.as_mut_ptr(), n_images, &mut n_images, out.as_mut_ptr(), out.len())
     };
     check(ctx, st)?; // an Err drops every image, like the `?` inside the reference's slice loops
     let imgs = images[..n_images]
@@ -96,6 +104,13 @@ fn read_to(target: c_int, buf: &[u8]) -> Result<(Header, Vec<Image<u8>>)> {
         .map(|im| Image { w: im.w, h: im.h, stride: im.stride, data: out[im.offset as usize..(im.offset + im.size) as usize].to_vec() })
         .collect();
     Ok((header, imgs))
+}
+
+/// A `.basis` file of either kind to the block format `target` (an `ffi::BU_TARGET_*` value; bu_read_file_to, no counterpart in the
+/// reference).  A UASTC file takes every format; an ETC1S file takes ETC1, RGBA32 and BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB, BC3_RGBA:
+/// one image per colour / alpha slice pair (per slice for ETC1 and in a file without alpha slices, where A = 255).
+pub fn read_file_to(target: c_int, buf: &[u8]) -> Result<Vec<Image<u8>>> {
+    read_with(ffi::bu_read_file_query, ffi::bu_read_file_to, target, buf).map(|r| r.1)
 }
 
 /// basis.rs:8-90
