@@ -45,6 +45,15 @@ void bu_emul_batch(int target, const uint8_t* in, size_t n_blocks, uint8_t* out,
     for (size_t i = 0; i < n_blocks; i++) st[i] = (uint8_t)bu_emul_block(target, in + 16 * i, out + obs * i);
 }
 size_t bu_emul_tables_size(void) { return sizeof(BuTablesAll); }
+// what the mode-sorted kernel of `target` sorts by (tests/sort_cases.py): its row of BU_COST_ORDER (cost_order[k] = the mode of run k; 19 = the invalid
+// mode codes) and of key_lut (key_lut[c] = the run of a block whose first seven bits are c).  Returns the row's number.
+int bu_emul_sort_tables(int target, uint8_t* cost_order, uint8_t* key_lut)
+{
+    const int row = bu_cost_row(target);
+    memcpy(cost_order, BU_COST_ORDER[row], 20);
+    memcpy(key_lut, tables().key_lut[row], 128);
+    return row;
+}
 // the launch plan of bu_uastc_transcode_batch_in_flight for a slice table given as ADDRESSES (nothing is dereferenced): rows of
 // (launch, in, out, n_blocks, index base), one per run or piece, in launch order; returns the number of rows (or the number needed
 // if `cap` is too small) and the number of launches in *out_launches
