@@ -22,7 +22,7 @@ SYMBOLS = [
     "bu_uastc_transcode", "bu_uastc_decode_to_rgba",
     "bu_unpack_uastc_block_to_rgba", "bu_transcode_uastc_block_to_astc", "bu_transcode_uastc_block_to_bc7",
     "bu_transcode_uastc_block_to_etc1", "bu_transcode_uastc_block_to_etc2", "bu_block_api_on_device", "bu_context_set_launch_policy", "bu_context_get_launch_policy", "bu_context_stream", "bu_context_synchronize", "bu_context_probe_streams", "bu_context_query_in_flight", "bu_uastc_transcode_device_sync",
-    "bu_uastc_transcode_device", "bu_uastc_transcode_batch_device", "bu_uastc_transcode_batch_in_flight", "bu_status_word_reset", "bu_status_word_decode", "bu_host_alloc", "bu_host_free",
+    "bu_uastc_transcode_device", "bu_uastc_transcode_batch_device", "bu_uastc_transcode_batch_in_flight", "bu_uastc_transcode_rects_device", "bu_status_word_reset", "bu_status_word_decode", "bu_host_alloc", "bu_host_free",
     "bu_etc1s_selector_from_rows", "bu_etc1s_transcode_etc1_device", "bu_etc1s_decode_rgba_device",
     "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode",
     "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_read_file_query", "bu_read_file_to", "bu_basislz_decode",
@@ -63,6 +63,12 @@ class SliceDesc(ctypes.Structure):  # bu_slice_desc == basis::SliceDesc (basis.r
 class ImageDesc(ctypes.Structure):  # bu_image
     _fields_ = [("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("stride", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("offset", ctypes.c_uint64), ("size", ctypes.c_uint64)]
+
+
+class RectJob(ctypes.Structure):  # bu_rect_job
+    _fields_ = [("d_in", ctypes.c_void_p), ("in_blocks_per_row", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
+                ("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("d_out", ctypes.c_void_p), ("out_pitch_bytes", ctypes.c_uint64),
+                ("index_base", ctypes.c_uint64)]
 
 
 _lib = None
@@ -173,6 +179,9 @@ def load():
     lib.bu_uastc_transcode_batch_device.restype = c.c_int
     lib.bu_uastc_transcode_batch_in_flight.argtypes = [vp, c.c_int, sz, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp), sz, c.POINTER(c.c_uint64), vp, c.c_int]
     lib.bu_uastc_transcode_batch_in_flight.restype = c.c_int
+    if hasattr(lib, "bu_uastc_transcode_rects_device"):  # (an older build under BASISU_HIP_LIB, for an A/B, lacks it: calling it there raises)
+        lib.bu_uastc_transcode_rects_device.argtypes = [vp, c.c_int, sz, c.POINTER(RectJob), vp, vp]
+        lib.bu_uastc_transcode_rects_device.restype = c.c_int
     lib.bu_time_uastc_launches_window.argtypes = [vp, c.c_int, c.POINTER(vp), c.POINTER(vp), sz, sz, sz, sz, c.c_int, c.c_int, vp, vp,
                                                   c.POINTER(c.c_float), c.POINTER(c.c_float), c.POINTER(c.c_int)]
     lib.bu_time_uastc_launches_window.restype = c.c_int

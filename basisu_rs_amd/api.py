@@ -259,6 +259,19 @@ class Context:
                                                           VP(*[_ptr(x) for x in d_outs]), int(blocks_per_row), ib, _ptr(d_status), int(n_streams))
         self._check(st)
 
+    def uastc_transcode_rects_device(self, fmt, jobs, d_status=None, stream=None):
+        """bu_uastc_transcode_rects_device: rectangles of slices into pitched surfaces, all in one call; only enqueues.  jobs: a sequence of
+        (d_in, in_blocks_per_row, x0, y0, w, h, d_out, out_pitch_bytes[, index_base]) -- d_in / d_out device tensors or raw pointers -- or _lib.RectJob"""
+        arr = (_lib.RectJob * len(jobs))()
+        for i, j in enumerate(jobs):
+            if isinstance(j, _lib.RectJob):
+                arr[i] = j
+                continue
+            d_in, bpr, x0, y0, w, h, d_out, pitch = j[:8]
+            arr[i] = _lib.RectJob(_ptr(d_in).value, int(bpr), int(x0), int(y0), int(w), int(h), _ptr(d_out).value, int(pitch), int(j[8]) if len(j) > 8 else 0)
+        st = self._lib.bu_uastc_transcode_rects_device(self._h, int(fmt), len(jobs), arr if len(jobs) else None, _ptr(d_status), _stream_ptr(stream))
+        self._check(st)
+
     def synchronize(self):
         """bu_context_synchronize: everything enqueued on the context's own streams has completed"""
         self._check(self._lib.bu_context_synchronize(self._h))

@@ -267,6 +267,39 @@ bu_status bu_uastc_transcode_batch_device(bu_context* ctx, bu_target target, siz
     return bu_launch_runs(ctx, target, runs.data(), runs.size(), blocks_per_row, d_status, static_cast<hipStream_t>(stream), -1);
 }
 
+// Rectangles of slices into pitched surfaces (include/basisu_hip.h): every job is checked before anything is enqueued, then the plan of bu_rect_plan.hpp is
+// launched -- the job table in the kernel arguments, nothing allocated, copied or freed behind the call.  The context's launch policy sizes the grid as it does
+// the multi-run launch's; AUTO is resolved where a launch holds more than one tile per CU.
+bu_status bu_uastc_transcode_rects_device(bu_context* ctx, bu_target target, size_t n_jobs, const bu_rect_job* jobs, uint64_t* d_status, void* stream)
+{
+    if (!ctx || bu_target_block_bytes(target) == 0 || (n_jobs && !jobs)) return BU_ERR_ARGUMENT;
+    if (n_jobs == 0) return BU_OK;
+    std::vector<BuRectJobIn> in(n_jobs);
+    for (size_t i = 0; i < n_jobs; i++) {
+        const bu_rect_job& j = jobs[i];
+        in[i] = BuRectJobIn{reinterpret_cast<uint64_t>(j.d_in), j.in_blocks_per_row, j.x0, j.y0, j.w, j.h, reinterpret_cast<uint64_t>(j.d_out), j.out_pitch_bytes, j.index_base};
+        if (!bu_rect_job_ok(target, in[i])) return BU_ERR_ARGUMENT;
+    }
+    const BuRectsFn k = bu_rects_kernels[target];
+    if (!k) return BU_ERR_ARGUMENT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BU_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned cu_count = (unsigned)ctx->cu_count;
+    std::vector<BuRectsLaunch> plan;
+    bu_plan_rects(target, in.data(), n_jobs, plan);
+    for (BuRectsLaunch& l : plan) {
+        int pol = ctx->launch_policy.load(std::memory_order_relaxed);
+        const bool big = bu_rects_needs_policy(l, cu_count);
+        if (pol == BU_POLICY_AUTO) pol = big ? bu_auto_policy(ctx, s) : (int)BU_POLICY_EXCLUSIVE;
+        else if (big) bu_note_big_enqueue(ctx, s);
+        bu_plan_rects_grid(target, pol, cu_count, l);
+        hipLaunchKernelGGL(k, dim3(l.grid), dim3(l.block), 0, s, l.table, (unsigned)l.n_tiles, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return bu_fail(ctx, e, "rectangle launch");
+    }
+    return BU_OK;
+}
+
 }  // extern "C"
 namespace {
 // launches groups[j] for j = first, first + step, ... on stream `s` (one stream's share of a pipelined batch, in order)

@@ -143,6 +143,13 @@ const std::array<BuMultiFn, 4> bu_multi_kernels[BU_N_TARGETS] = {bu_multi_fns<BU
                                                                  bu_multi_fns<BU_TGT_BC5>(), bu_multi_fns<BU_TGT_R11>(), bu_multi_fns<BU_TGT_RG11>(), {},
                                                                  bu_multi_fns<BU_TGT_BC1>(), bu_multi_fns<BU_TGT_BC3>()};
 
+// the rectangle kernels (bu_uastc_transcode_rects_device): one per target
+using BuRectsFn = decltype(&bu_uastc_rects_kernel<BU_TGT_BC7>);
+const BuRectsFn bu_rects_kernels[BU_N_TARGETS] = {bu_uastc_rects_kernel<BU_TGT_ASTC>, bu_uastc_rects_kernel<BU_TGT_BC7>, bu_uastc_rects_kernel<BU_TGT_ETC1>,
+                                                  bu_uastc_rects_kernel<BU_TGT_ETC2>, bu_uastc_rects_kernel<BU_TGT_RGBA>, nullptr, bu_uastc_rects_kernel<BU_TGT_BC4>,
+                                                  bu_uastc_rects_kernel<BU_TGT_BC5>, bu_uastc_rects_kernel<BU_TGT_R11>, bu_uastc_rects_kernel<BU_TGT_RG11>, nullptr,
+                                                  bu_uastc_rects_kernel<BU_TGT_BC1>, bu_uastc_rects_kernel<BU_TGT_BC3>};
+
 // One slice: resolve the policy, plan (bu_plan_slice), claim tile tickets where the plan asks for them, launch.
 // policy = BU_POLICY_* of this launch, or -1 for the context's (bu_context_set_launch_policy; BU_POLICY_AUTO there is resolved per launch by
 // bu_auto_policy): only the device-pointer slice entry points pass -1 -- the host-pointer and whole-file entry points issue their launches one

@@ -209,7 +209,8 @@ struct BuTileDesc {
     uint32_t width;   // rectangles: blocks per row of the run's (virtual) grid; 0: strips
 };
 enum { BU_LAYOUT_STRIP = 0, BU_LAYOUT_RECT = 1, BU_LAYOUT_MULTI = 2,
-       BU_LAYOUT_MULTI_WHOLE = 3 };  // MULTI with every run tiled as whole rectangles (BuRunDesc::vshift): no lane ever lacks a block, and the validity tests fold away as in RECT
+       BU_LAYOUT_MULTI_WHOLE = 3,    // MULTI with every run tiled as whole rectangles (BuRunDesc::vshift): no lane ever lacks a block, and the validity tests fold away as in RECT
+       BU_LAYOUT_RECTS = 4 };        // several RECTANGLES cut out of slices, each stored at a pitch of its own (bu_uastc_rects_kernel below; table and address mapping: bu_rect_plan.hpp)
 // one set of tile tickets (kernel, `ticket`): eight counters BU_TICKET_STRIDE words apart, then the count of workgroups that have left
 constexpr unsigned BU_TICKET_STRIDE = 32, BU_TICKET_DONE = 8 * BU_TICKET_STRIDE, BU_TICKET_WORDS = 9 * BU_TICKET_STRIDE;
 // WGS threads per workgroup, BPT blocks per thread: tile = WGS * BPT blocks.  PREFETCH: a workgroup that walks several tiles
@@ -218,7 +219,8 @@ template <int TARGET, int WGS, int BPT, bool PREFETCH, int LAYOUT>
 __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ in, void* __restrict__ out, unsigned n_blocks,
                                                      unsigned bpr, unsigned long long base, unsigned long long* status,
                                                      const BuTablesAll* __restrict__ tables, unsigned cus, unsigned tile_rt,
-                                                     const BuRunTable* __restrict__ runs, unsigned* __restrict__ ticket = nullptr)
+                                                     const BuRunTable* __restrict__ runs, unsigned* __restrict__ ticket = nullptr,
+                                                     const BuRectTable* __restrict__ rects = nullptr)
 {
     // Static priority by residency generation.  Workgroups are dealt breadth-first (b, b + CUs, b + 2 CUs, ... share a CU:
     // tools/exp/census.hip), and the instruction arbiter serves the OLDEST wave first, so the four tiles of a CU finish
@@ -245,6 +247,12 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // which is what lets two workgroups share a CU.
     constexpr bool RECT = LAYOUT == BU_LAYOUT_RECT, MULTI = LAYOUT == BU_LAYOUT_MULTI || LAYOUT == BU_LAYOUT_MULTI_WHOLE;
     constexpr bool WHOLE = RECT || LAYOUT == BU_LAYOUT_MULTI_WHOLE;  // every tile of the launch holds BU_TILE blocks
+    // RECTS: the tiles of several rectangles (a table in the kernel arguments, as MULTI's), each 2^tshift x (BU_TILE >> tshift) blocks of its rectangle, clipped at the
+    // rectangle's right and bottom edge, loaded at the slice's pitch and stored at the output's.  Only where a block comes from, whether a lane has one and where its
+    // result goes differ from the other layouts; the sort, the chunk phase and the block code do not know.
+    constexpr bool RECTS = LAYOUT == BU_LAYOUT_RECTS;
+    static_assert(!RECTS || (BU_TILE == (int)BU_RECTS_TILE && PREFETCH), "the host numbers 1024-block tiles of rectangles; one compiled shape");
+    constexpr uint32_t RECTS_ROW_BYTES = bu_rect_row_bytes(TARGET), RECTS_ROWS = bu_rect_rows_per_block(TARGET);
     constexpr bool BU_ALIAS = TARGET == BU_TGT_RGBA;
     // two RGBA32 workgroups must fit the 160 KiB of a CU: output tile + table blob + status bytes + counters / chunk list
     static_assert(!BU_ALIAS || bu_lds_table_bytes(TARGET) + 4 * BU_TILE * 16 + BU_TILE + 1536 <= 80 * 1024,
@@ -313,10 +321,13 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // MULTI, persistent grid: the run table is copied to LDS once per workgroup (3.9 KiB) and every later look-up reads it there.  From the kernel
     // arguments a look-up is two vector loads, a ballot and dependent scalar loads -- a microsecond of round trips between the scatter and the prefetch
     // loads of EVERY tile, with the workgroup waiting at barrier (2) behind it (8 % of a multi-run launch over 2^20-block slices)
-    constexpr bool RUNS_IN_LDS = MULTI && PREFETCH;
-    __shared__ uint4 s_runs[RUNS_IN_LDS ? sizeof(BuRunTable) / 16 : 1];  // (16 bytes in every other instantiation)
+    constexpr bool RUNS_IN_LDS = (MULTI || RECTS) && PREFETCH;
+    __shared__ uint4 s_runs[RUNS_IN_LDS ? (RECTS ? sizeof(BuRectTable) : sizeof(BuRunTable)) / 16 : 1];  // (16 bytes in every other instantiation)
     const BuRunTable* R = runs;  // the table the look-ups read: the kernel arguments until the copy is complete (the first barrier), LDS from then on
-    if constexpr (RUNS_IN_LDS) {
+    const BuRectTable* Q = rects;  // RECTS: the job table, read where `R` is
+    if constexpr (RUNS_IN_LDS && RECTS) {
+        for (unsigned i = tid; i < sizeof(BuRectTable) / 16; i += WGS) s_runs[i] = reinterpret_cast<const uint4*>(rects)[i];
+    } else if constexpr (RUNS_IN_LDS) {
         static_assert(sizeof(BuRunTable) % 16 == 0, "copied in 16-byte pieces");
         for (unsigned i = tid; i < sizeof(BuRunTable) / 16; i += WGS) s_runs[i] = reinterpret_cast<const uint4*>(runs)[i];
     }
@@ -353,15 +364,31 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             }
         }
     };
+    // RECTS: `qd` / `ql` are what `td` / `tl` are to MULTI; tile t belongs to the last job whose first tile is <= t (first_tile[0] = 0: there is one)
+    BuRectTile qd = {}, ql = {};
+    auto rect_of = [&](unsigned t, BuRectTile& d) {
+        if constexpr (RECTS) {
+            if (t < n_tiles) {
+                static_assert(BU_RECT_JOBS == 64, "one first-tile number per lane");
+                const uint32_t r = uni32((uint32_t)__popcll(__ballot(Q->first_tile[lane] <= t)) - 1u);
+                const BuRectDesc jv = Q->job[r];  // (every lane reads the same record: made scalar, as MULTI's)
+                const BuRectDesc jd = {uni64(jv.in), uni64(jv.out), uni64(jv.pitch), uni64(jv.base), uni32(jv.in_bpr), uni32(jv.w), uni32(jv.h), uni32(jv.tpr)};
+                d = bu_rect_tile(jd, t - uni32(Q->first_tile[r]), RECTS_ROW_BYTES, RECTS_ROWS);
+            }
+        }
+    };
     desc_of(tile, td);
     tl = td;
+    rect_of(tile, qd);
+    ql = qd;
     // block l of tile t (whose descriptor is `tl`): where it is loaded from, whether it exists
     // MULTI: block l of the tile described by d, as an index inside d's run (strips: consecutive; rectangles: row l / 64, column l % 64 of the tile)
     auto run_idx = [&](const BuTileDesc& d, unsigned l) { return d.first + ((WHOLE || d.width) ? (l / BU_RECT_W) * d.width + (l % BU_RECT_W) : l); };
-    auto blk_src = [&](unsigned t, unsigned l) { return MULTI ? tl.in + run_idx(tl, l) : in + gidx(t, l); };
-    auto ld_blk = [&](unsigned t, unsigned l) { return MULTI ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
+    auto blk_src = [&](unsigned t, unsigned l) { return RECTS ? reinterpret_cast<const uint4*>(bu_rect_src(ql, l)) : MULTI ? tl.in + run_idx(tl, l) : in + gidx(t, l); };
+    auto ld_blk = [&](unsigned t, unsigned l) { return (MULTI || RECTS) ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
     auto blk_valid = [&](unsigned t, unsigned l) {
-        if constexpr (MULTI) return t < n_tiles && (WHOLE || l < tl.n);
+        if constexpr (RECTS) return t < n_tiles && bu_rect_has(ql, l);
+        else if constexpr (MULTI) return t < n_tiles && (WHOLE || l < tl.n);
         else return RECT ? t < n_tiles : (t < n_tiles && gidx(t, l) < n_blocks && in_tile(l));
     };
     // Table staging.  The staged 16-byte pieces of the LDS image are numbered 0..TVT-1: BC7's own tables, then the target's one or
@@ -408,7 +435,8 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     if (tid < 64) (&cnt[0][0])[tid] = 0;
     if (tid < 2) next_chunk[tid] = 0;
     __syncthreads();
-    if constexpr (RUNS_IN_LDS) R = reinterpret_cast<const BuRunTable*>(s_runs);
+    if constexpr (RUNS_IN_LDS && RECTS) Q = reinterpret_cast<const BuRectTable*>(s_runs);
+    else if constexpr (RUNS_IN_LDS) R = reinterpret_cast<const BuRunTable*>(s_runs);
     unsigned par = 0;
     unsigned next_of_loop = 0;
     // STORES_LAST (the multi-run BC7 / ASTC kernels with PREFETCH): a tile's result stores are the LAST thing its iteration issues.  vmcnt counts loads and stores in issue order and
@@ -453,7 +481,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             if constexpr (STORES_LAST) {
                 key[j] = next_key[j];
             } else {
-                const bool valid = WHOLE || (MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
+                const bool valid = WHOLE || (RECTS ? bu_rect_has(qd, (unsigned)(j * BU_WG) + tid) : MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
                 key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
             }
             uniform = uniform && (__ballot(key[j] == (uint32_t)__builtin_amdgcn_readfirstlane(key[j])) == ~0ull) && has_block(key[j]);
@@ -502,6 +530,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         uint4 vn[BU_BPT];
         if constexpr (PREFETCH) {
             desc_of(ntile, tl);
+            rect_of(ntile, ql);
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) {
                 vn[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
@@ -591,6 +620,33 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         } else {
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
+            if constexpr (RECTS) {  // the three write-back forms at the job's pitch: 16-byte blocks, 8-byte blocks, RGBA32's four pixel rows
+                if (has_block(key[j])) {
+                    const unsigned l = j * BU_WG + tid;
+                    const unsigned long long blk = qd.base + bu_rect_idx(qd, l);
+                    const uint64_t dst = bu_rect_dst(qd, l, RECTS_ROW_BYTES, RECTS_ROWS);
+                    if constexpr (INBLOCK) {
+                        uint4 r = sblk[dest[j]];
+                        if ((r.x & 0xFFu) == 0u) {  // (as below)
+                            bu_report(status, blk, (int)r.w);
+                            r.w = 0;
+                        }
+                        bu_st_stream(reinterpret_cast<uint4*>(dst), r);
+                    } else {
+                        const uint32_t st = sst[dest[j]];
+                        if (st) bu_report(status, blk, (int)st);
+                        if constexpr (TARGET == BU_TGT_RGBA) {
+#pragma unroll
+                            for (int r = 0; r < 4; r++) bu_st_stream(reinterpret_cast<uint4*>(dst + (uint64_t)r * qd.pitch), sout[r * BU_TILE + dest[j]]);
+                        } else {
+                            const uint4 r = sblk[dest[j]];
+                            if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(dst), make_uint2(r.x, r.y));
+                            else bu_st_stream(reinterpret_cast<uint4*>(dst), r);
+                        }
+                    }
+                }
+                continue;
+            }
             if (has_block(key[j])) {
                 const unsigned idx = MULTI ? run_idx(td, j * BU_WG + tid) : gidx(tile, j * BU_WG + tid);  // (MULTI: inside the tile's slice)
                 void* const out = td.out;                  // (the launch's `out` unless MULTI)
@@ -633,9 +689,12 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) v[j] = vn[j];
             td = tl;
+            qd = ql;
         } else {
             desc_of(ntile, tl);
             td = tl;
+            rect_of(ntile, ql);
+            qd = ql;
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
         }
@@ -677,6 +736,16 @@ __global__ __launch_bounds__(WGS, (TARGET == BU_TGT_ASTC && WGS == 512) ? 8 : bu
     static_assert(sizeof(BuRunTable) + 40 <= 4096, "the run table and the other arguments share the 4 KiB of kernel arguments");
     bu_uastc_sorted_body<TARGET, WGS, BPT, PREFETCH, WHOLE ? BU_LAYOUT_MULTI_WHOLE : BU_LAYOUT_MULTI>(nullptr, nullptr, n_tiles * (unsigned)(WGS * BPT), bpr, 0ull, status, tables, 0u,
                                                                                                         (unsigned)(WGS * BPT), &table, ticket);
+}
+
+// rectangles of slices into pitched surfaces in one launch (layout RECTS; bu_uastc_transcode_rects_device): n_tiles tiles over the jobs of `table` (a kernel
+// argument, by value; copied to LDS once per workgroup), a persistent grid in the multi-run launch's 512 x 2 shape with the next tile's loads in flight.  One
+// instantiation per target; no tile tickets.  (ASTC is NOT held to 64 VGPRs here as its multi-run kernel of this shape is: that bound costs it a spill.)
+template <int TARGET>
+__global__ __launch_bounds__(512) void bu_uastc_rects_kernel(const BuRectTable table, unsigned n_tiles, unsigned long long* status, const BuTablesAll* __restrict__ tables)
+{
+    static_assert(sizeof(BuRectTable) + 24 <= 4096, "the job table and the other arguments share the 4 KiB of kernel arguments");
+    bu_uastc_sorted_body<TARGET, 512, 2, true, BU_LAYOUT_RECTS>(nullptr, nullptr, n_tiles * BU_RECTS_TILE, 0u, 0ull, status, tables, 0u, BU_RECTS_TILE, nullptr, nullptr, &table);
 }
 
 // status words back to "no failing block".  A kernel, not hipMemsetAsync: the reset is part of what callers capture into

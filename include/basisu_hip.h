@@ -215,6 +215,35 @@ bu_status bu_uastc_transcode_device(bu_context* ctx, bu_target target, const voi
 bu_status bu_uastc_transcode_batch_device(bu_context* ctx, bu_target target, size_t n_slices, const void* const* d_in,
                                           const size_t* n_blocks, void* const* d_out, size_t blocks_per_row,
                                           const uint64_t* index_base, uint64_t* d_status, void* stream);
+/* RECTANGLES of slices into PITCHED surfaces, many in one call: pages of a virtual texture or atlas regions cut out of slices resident in device memory, each
+ * written to its slot of a page cache, an upload buffer with a row alignment or a sub-region of a larger atlas -- without a tight scratch buffer and a 2-D copy
+ * behind it, and without one launch per block row of a page.
+ *   For every job and every 0 <= x < w, 0 <= y < h the bytes written for block (x, y) are exactly what bu_uastc_transcode_device writes for block
+ *   (y0 + y) * in_blocks_per_row + (x0 + x) of the whole slice, a failing block's zeros included.  Block-linear targets write them at
+ *   d_out + y * out_pitch_bytes + x * block_bytes; RGBA32 writes pixel row r of the block (16 bytes) at d_out + (4 y + r) * out_pitch_bytes + 16 x.
+ *   No byte outside those positions is written (pitch padding and neighbouring content survive), and no block outside a rectangle is read: a failing block of
+ *   the slice that lies in no rectangle is never reported, and nothing in front of d_in or behind the slice row of the rectangle's last block is touched.
+ *   d_status (optional, as above): min over the failing blocks of all jobs of (index_base + (y0 + y) * in_blocks_per_row + (x0 + x)) << 8 | status.
+ * Argument rules, all checked for EVERY job before anything is enqueued (BU_ERR_ARGUMENT, nothing launched): a valid target; jobs non-NULL unless n_jobs == 0
+ * (BU_OK, nothing done); d_in, d_out non-NULL; w, h, in_blocks_per_row >= 1; x0 + w <= in_blocks_per_row; (y0 + h) * in_blocks_per_row <= 2^32; d_in 16-byte
+ * aligned; d_out and out_pitch_bytes multiples of the block size (8 for the 8-byte targets, else 16, RGBA32 included); out_pitch_bytes >= w * block size
+ * (RGBA32: >= 16 w).  Outputs of different jobs must not overlap and no output may alias an input (the caller's duty, unchecked); jobs may read the same slice,
+ * even the same blocks.
+ * The call only enqueues on `stream`: the job table travels in the kernel arguments (64 jobs per launch; longer lists go out as several launches, in order),
+ * nothing is allocated, copied from the host asynchronously, freed or synchronised behind it, `jobs` may be reused when it returns, and it may be recorded by
+ * stream capture and replayed.  It follows the context's launch policy as the batch call does and draws no tile tickets.  Tiles are cut per job: 64 / 32 / 16 / 8
+ * blocks wide (the smallest not below min(w, 64)) and 1024 / width high, so a 32 x 32-block page is exactly one tile. */
+typedef struct bu_rect_job {
+    const void* d_in;            /* block (0,0) of the SLICE the rectangle is cut from; 16-byte aligned */
+    uint32_t in_blocks_per_row;  /* width of that slice's block grid, >= 1 */
+    uint32_t x0, y0;             /* first block column / block row of the rectangle inside the slice */
+    uint32_t w, h;               /* size in blocks, both >= 1; x0 + w <= in_blocks_per_row */
+    void* d_out;                 /* where the rectangle's block (0,0) goes (RGBA32: its pixel (0,0)) */
+    uint64_t out_pitch_bytes;    /* from one block row of the output to the next (RGBA32: one PIXEL row to the next) */
+    uint64_t index_base;         /* added to the block's slice index (y0+y)*in_blocks_per_row + (x0+x) in the status word */
+} bu_rect_job;
+bu_status bu_uastc_transcode_rects_device(bu_context* ctx, bu_target target, size_t n_jobs, const bu_rect_job* jobs /* HOST array */, uint64_t* d_status,
+                                          void* stream);
 /* The same loop over independent slices at the rate of a PIPELINE of launches -- what bench.py's headline measures, as one call.
  * Launches queued on one stream never overlap, and a launch over a slice waits for HBM with the ALUs idle and then computes with HBM idle;
  * launches on several streams fill each other's gaps (UASTC -> BC7 over 4096 x 4096 slices: 8.4 us per slice one at a time, 5.6-6.0 us in a

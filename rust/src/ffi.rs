@@ -101,6 +101,21 @@ pub struct bu_image {
     pub size: u64,
 }
 
+/// bu_rect_job: one rectangle of a slice and the pitched surface it is transcoded into (bu_uastc_transcode_rects_device)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bu_rect_job {
+    pub d_in: *const c_void,
+    pub in_blocks_per_row: u32,
+    pub x0: u32,
+    pub y0: u32,
+    pub w: u32,
+    pub h: u32,
+    pub d_out: *mut c_void,
+    pub out_pitch_bytes: u64,
+    pub index_base: u64,
+}
+
 extern "C" {
     pub fn bu_context_create(device: c_int, out_ctx: *mut *mut bu_context) -> c_int;
     pub fn bu_context_destroy(ctx: *mut bu_context);
@@ -190,4 +205,12 @@ extern "C" {
     pub fn bu_device_alloc(ctx: *mut bu_context, bytes: usize, out_ptr: *mut *mut c_void) -> c_int;
     pub fn bu_device_free(ctx: *mut bu_context, ptr: *mut c_void) -> c_int;
     pub fn bu_memcpy(ctx: *mut bu_context, dst: *mut c_void, src: *const c_void, bytes: usize, to_device: c_int) -> c_int;
+}
+
+// rectangles of slices into pitched surfaces, device pointers, asynchronous.  A block of its own: its job array is a struct the type-level sweep of
+// tests/test_capi_symbols.py has no spelling for; tests/test_rect_capi.py checks this declaration and the struct above against the header.
+// Crate-visible; users of the crate reach it through `transcode_rects_device` of lib.rs, which takes the jobs as a slice.
+extern "C" {
+    pub(crate) fn bu_uastc_transcode_rects_device(ctx: *mut bu_context, target: c_int, n_jobs: usize, jobs: *const bu_rect_job, d_status: *mut u64,
+                                                  stream: *mut c_void) -> c_int;
 }

@@ -5,7 +5,8 @@
 //!   read_to_rgba / read_to_etc1 / read_to_etc2 / read_to_uastc / read_to_astc / read_to_bc7   (basis.rs:8-260)
 //!   unpack_uastc_block_to_rgba, transcode_uastc_block_to_{astc,bc7,etc1,etc2}                   (lib.rs:29-53)
 //!   Image<T>, Header                                                                            (lib.rs:63-68, basis.rs:417-473)
-//! plus `transcode_array_sharded`, the multi-device entry the reference has no counterpart for.
+//! plus `transcode_array_sharded`, the multi-device entry, and `transcode_rects_device` (rectangles of resident slices into pitched surfaces), which
+//! the reference has no counterparts for.
 pub mod ffi;
 
 use std::ffi::CStr;
@@ -191,6 +192,19 @@ pub fn transcode_slice(format: TargetTextureFormat, data: &[u8]) -> Result<Vec<u
     let mut bad = 0u64;
     check(ctx, unsafe { ffi::bu_uastc_transcode(ctx, format as c_int, data.as_ptr(), data.len(), out.as_mut_ptr(), out.len(), &mut bad) })?;
     Ok(out)
+}
+
+/// Rectangles of device-resident UASTC slices into pitched surfaces, all `jobs` in one enqueue on `stream` (bu_uastc_transcode_rects_device, no
+/// counterpart in the reference): pages of a virtual texture into their slots of a page cache, a slice into an upload buffer with a row alignment or
+/// into a region of a larger atlas.  `target` is an `ffi::BU_TARGET_*` value, `d_status` an optional device status word.  Only argument and launch
+/// errors are returned; `jobs` may be dropped when the call returns.
+///
+/// # Safety
+/// `ctx` is a live context; every `d_in` / `d_out` of `jobs` and `d_status` (unless null) are device pointers of its device that cover what the jobs
+/// name; outputs overlap neither each other nor an input; `stream` is null or a stream of that device.
+pub unsafe fn transcode_rects_device(ctx: *mut ffi::bu_context, target: c_int, jobs: &[ffi::bu_rect_job], d_status: *mut u64,
+                                     stream: *mut core::ffi::c_void) -> Result<()> {
+    check(ctx, ffi::bu_uastc_transcode_rects_device(ctx, target, jobs.len(), jobs.as_ptr(), d_status, stream))
 }
 
 /// Texture array sharded over the devices `devices` of one node (no counterpart in the reference, which walks the slices

@@ -1,0 +1,301 @@
+"""bu_uastc_transcode_rects_device on the GPU: rectangles of slices into pitched surfaces, many per call.
+
+The test slice is 200 x 40 blocks, block i = known-answer vector i mod 608: every mode is present and every tile is mixed.  Expected bytes are the
+reference's known answers (tests/golden/uastc_kat.bin) for ASTC / BC7 / ETC1 / ETC2 / RGBA32 and bu_uastc_transcode_device over the whole slice -- which its
+own tests pin -- for the six other targets.  Every surface is pre-filled with a poison byte and sits between guard bands (tests/gpu_guard.py): every position
+of a rectangle is compared, every other byte must still be poison, and the slices sit between bands of invalid blocks, so a lane that took a block outside
+its slice would report it."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from basisu_rs_amd import _lib
+
+pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+TARGETS = {"astc": _lib.ASTC, "bc7": _lib.BC7, "etc1": _lib.ETC1, "etc2": _lib.ETC2, "rgba": _lib.RGBA32, "bc4": _lib.BC4_R, "bc5": _lib.BC5_RG,
+           "r11": _lib.EAC_R11, "rg11": _lib.EAC_RG11, "bc1": _lib.BC1_RGB, "bc3": _lib.BC3_RGBA}
+KAT = ("astc", "bc7", "etc1", "etc2", "rgba")  # the targets the reference's known answers cover
+NBX, NBY = 200, 40
+RECTS = ((0, 0, 200, 40), (7, 3, 1, 1), (5, 1, 63, 15), (64, 16, 64, 16), (3, 2, 65, 17), (190, 0, 10, 40), (0, 39, 200, 1), (11, 5, 32, 32))
+POISON = 0xA5
+CLEAR = _lib.STATUS_WORD_CLEAR
+BAD_MODE = 0x45  # the one invalid 7-bit mode code: "invalid mode index", BU_ERR_INVALID_MODE
+
+
+def row_bytes(name):
+    """bytes a block takes of one output row (RGBA32: one of its four pixel rows)"""
+    return 16 if name == "rgba" else _lib.BLOCK_BYTES[TARGETS[name]]
+
+
+def rows_per_block(name):
+    return 4 if name == "rgba" else 1
+
+
+def slice_blocks(golden, k):
+    """slice k of the tests: block i = known-answer vector (i + 101 k) mod 608; slice 0 is the 200 x 40 slice every check uses"""
+    idx = (np.arange(NBX * NBY) + 101 * k) % 608
+    return idx, np.ascontiguousarray(golden["uastc"][idx])
+
+
+class Slice:
+    """a slice in device memory between bands of invalid blocks, and what every target makes of it"""
+
+    def __init__(self, ctx, golden, blocks, idx=None, nbx=NBX, names=tuple(TARGETS)):
+        import torch
+        from gpu_guard import Arena
+
+        self.nbx, self.n = nbx, blocks.shape[0]
+        self.arena = Arena("slice", [blocks.size], 16 * 1024, fill="uastc")
+        self.arena.data(0).copy_(torch.from_numpy(blocks.reshape(-1)).cuda())
+        self.ptr = self.arena.ptr(0)
+        self.want = {}
+        for name in names:
+            t = TARGETS[name]
+            if name in KAT and idx is not None:
+                self.want[name] = golden[name][idx]
+            else:  # the plain launch over the whole slice
+                out = torch.zeros(self.n * _lib.BLOCK_BYTES[t], dtype=torch.uint8, device="cuda")
+                ctx.transcode_device(t, self.ptr, self.n, out, nbx)
+                torch.cuda.synchronize()
+                got = out.cpu().numpy()
+                if name == "rgba":  # the image back to 64 bytes per block, pixel row by pixel row
+                    got = got.reshape(self.n // nbx, 4, nbx, 16).transpose(0, 2, 1, 3)
+                self.want[name] = np.ascontiguousarray(got).reshape(self.n, -1)
+
+    def rect(self, name, x0, y0, w, h):
+        """the bytes of the rectangle's surface rows, tight: (h * rows per block, w * row bytes)"""
+        y, x = np.meshgrid(np.arange(y0, y0 + h), np.arange(x0, x0 + w), indexing="ij")
+        b = self.want[name][y * self.nbx + x]  # (h, w, block bytes)
+        if name == "rgba":
+            return b.reshape(h, w, 4, 16).transpose(0, 2, 1, 3).reshape(4 * h, 16 * w)
+        return b.reshape(h, -1)
+
+
+@pytest.fixture(scope="module")
+def slices(ctx, golden):
+    out = []
+    for k in range(3):
+        idx, blocks = slice_blocks(golden, k)
+        out.append(Slice(ctx, golden, blocks, idx))
+    return out
+
+
+class Surfaces:
+    """one poisoned surface per job, each between guard bands of one arena; jobs: (slice, x0, y0, w, h, pitch, index_base)"""
+
+    def __init__(self, name, jobs):
+        from gpu_guard import Arena
+
+        self.name, self.jobs = name, jobs
+        rb, rpb = row_bytes(name), rows_per_block(name)
+        self.sizes = [rpb * h * pitch for (_, _, _, _, h, pitch, _) in jobs]
+        # (every other surface starts one block past 256-byte alignment: the smallest alignment the call allows)
+        self.arena = Arena("surfaces", self.sizes, 64 * 1024, offsets=[rb * (i % 2) for i in range(len(jobs))])
+        self.poison()
+
+    def poison(self):
+        for i in range(len(self.jobs)):
+            self.arena.data(i).fill_(POISON)
+
+    def table(self):
+        return [(s.ptr, s.nbx, x0, y0, w, h, self.arena.ptr(i), pitch, base) for i, (s, x0, y0, w, h, pitch, base) in enumerate(self.jobs)]
+
+    def check(self, untouched=False):
+        rb, rpb = row_bytes(self.name), rows_per_block(self.name)
+        self.arena.check()
+        for i, (s, x0, y0, w, h, pitch, _) in enumerate(self.jobs):
+            got = self.arena.data(i).cpu().numpy().reshape(rpb * h, pitch)
+            if untouched:
+                assert (got == POISON).all(), "job %d: something was written" % i
+                continue
+            want = s.rect(self.name, x0, y0, w, h)
+            assert np.array_equal(got[:, :w * rb], want), "job %d (%d, %d, %d, %d) pitch %d: the rectangle's bytes differ" % (i, x0, y0, w, h, pitch)
+            assert (got[:, w * rb:] == POISON).all(), "job %d (%d, %d, %d, %d) pitch %d: padding was written" % (i, x0, y0, w, h, pitch)
+
+
+def pitches(name, w):
+    rb = row_bytes(name)
+    return {"tight": w * rb, "padded": w * rb + rb, "4096": 4096 if 4096 >= w * rb else w * rb}
+
+
+def status_word():
+    import torch
+
+    return torch.zeros(1, dtype=torch.int64, device="cuda")
+
+
+def word_of(st):
+    return int(st.item()) & (2**64 - 1)
+
+
+@pytest.mark.parametrize("pitch", ["tight", "padded", "4096"])
+@pytest.mark.parametrize("name", list(TARGETS))
+def test_eight_rectangles_in_one_call(ctx, slices, name, pitch):
+    import torch
+
+    s = slices[0]
+    surf = Surfaces(name, [(s, x0, y0, w, h, pitches(name, w)[pitch], 0) for (x0, y0, w, h) in RECTS])
+    st = status_word()
+    ctx.status_word_reset(st)
+    ctx.uastc_transcode_rects_device(TARGETS[name], surf.table(), d_status=st)
+    torch.cuda.synchronize()
+    surf.check()
+    s.arena.check()
+    assert word_of(st) == CLEAR  # (nothing of the invalid blocks around the slice was taken)
+
+
+@pytest.mark.parametrize("name", list(TARGETS))
+def test_150_jobs_from_three_slices_in_one_call(ctx, slices, name):
+    """more jobs than one launch's table holds: several launches on the stream, in order"""
+    import torch
+
+    rng = np.random.default_rng(150)
+    rb, jobs = row_bytes(name), []
+    for i in range(150):
+        w, h = int(rng.integers(1, 41)), int(rng.integers(1, 41))
+        x0, y0 = int(rng.integers(0, NBX - w + 1)), int(rng.integers(0, NBY - h + 1))
+        jobs.append((slices[i % 3], x0, y0, w, h, w * rb + rb * int(rng.choice([0, 1, 5])), 1000 * i))
+    surf = Surfaces(name, jobs)
+    st = status_word()
+    ctx.status_word_reset(st)
+    ctx.uastc_transcode_rects_device(TARGETS[name], surf.table(), d_status=st)
+    torch.cuda.synchronize()
+    surf.check()
+    assert word_of(st) == CLEAR
+
+
+@pytest.mark.parametrize("name", ["astc", "bc7", "etc1", "etc2", "rgba", "bc4", "bc3"])
+def test_status_word(ctx, golden, name):
+    """an invalid-mode block inside two different jobs and one that lies in no job: the word names the lowest index_base + slice index of the first two,
+    with the reference's status; with only the outside block bad it stays clear"""
+    import torch
+
+    idx, blocks = slice_blocks(golden, 0)
+    rects = ((5, 1, 63, 15, 70000), (64, 16, 64, 16, 0), (11, 25, 32, 10, 1 << 40))
+    in_a, in_b, outside = 9 * NBX + 30, 20 * NBX + 100, 38 * NBX + 199  # (30, 9) in job 0, (100, 20) in job 1, (199, 38) in none
+    for bad, want in (((in_a, in_b, outside), (0 + in_b) << 8 | _lib.ERR_INVALID_MODE), ((outside,), CLEAR), ((in_a, outside), (70000 + in_a) << 8 | _lib.ERR_INVALID_MODE)):
+        b = blocks.copy()
+        for i in bad:
+            b[i, 0] = BAD_MODE
+        s = Slice(ctx, golden, b, names=(name,))  # (expected bytes: the plain launch over this slice -- zeros for the failing blocks)
+        for i in bad:
+            assert not s.want[name][i].any()
+        surf = Surfaces(name, [(s, x0, y0, w, h, pitches(name, w)["padded"], base) for (x0, y0, w, h, base) in rects])
+        st = status_word()
+        ctx.status_word_reset(st)
+        ctx.uastc_transcode_rects_device(TARGETS[name], surf.table(), d_status=st)
+        torch.cuda.synchronize()
+        assert word_of(st) == want
+        surf.check()
+        # without a status word the same call writes the same bytes
+        surf.poison()
+        ctx.uastc_transcode_rects_device(TARGETS[name], surf.table())
+        torch.cuda.synchronize()
+        surf.check()
+
+
+def test_argument_rules_and_nothing_launched(ctx, slices):
+    import torch
+
+    from basisu_rs_amd import BasisuError
+
+    s = slices[0]
+    for name in ("bc7", "etc1", "rgba"):
+        rb = row_bytes(name)
+        surf = Surfaces(name, [(s, x0, y0, w, h, pitches(name, w)["padded"], 0) for (x0, y0, w, h) in RECTS[1:5]])
+        good = surf.table()
+
+        def refused(last, target=TARGETS[name]):
+            with pytest.raises(BasisuError) as e:
+                ctx.uastc_transcode_rects_device(target, good[:-1] + [tuple(last)])
+            assert e.value.status == _lib.ERR_ARGUMENT
+            torch.cuda.synchronize()
+            surf.check(untouched=True)  # a bad argument in the LAST job: the jobs in front of it were not launched either
+
+        d_in, bpr, x0, y0, w, h, d_out, pitch, base = good[-1]
+        refused((0, bpr, x0, y0, w, h, d_out, pitch, base))
+        refused((d_in, bpr, x0, y0, w, h, 0, pitch, base))
+        refused((d_in, bpr, x0, y0, 0, h, d_out, pitch, base))
+        refused((d_in, bpr, x0, y0, w, 0, d_out, pitch, base))
+        refused((d_in, 0, 0, y0, w, h, d_out, pitch, base))
+        refused((d_in, bpr, bpr - w + 1, y0, w, h, d_out, pitch, base))           # x0 + w > in_blocks_per_row
+        refused((d_in, 1 << 21, 0, 2048 - h + 1, w, h, d_out, pitch, base))      # (y0 + h) * in_blocks_per_row > 2^32
+        refused((d_in + 8, bpr, x0, y0, w, h, d_out, pitch, base))               # d_in not 16-byte aligned
+        refused((d_in, bpr, x0, y0, w, h, d_out + rb // 2, pitch, base))         # d_out no multiple of the block size
+        refused((d_in, bpr, x0, y0, w, h, d_out, pitch + rb // 2, base))         # nor the pitch
+        refused((d_in, bpr, x0, y0, w, h, d_out, w * rb - rb, base))             # pitch below the row
+        refused(good[-1], target=5)
+        refused(good[-1], target=10)
+        lib = _lib.load()
+        assert lib.bu_uastc_transcode_rects_device(ctx.handle, TARGETS[name], 2, None, None, None) == _lib.ERR_ARGUMENT
+        assert lib.bu_uastc_transcode_rects_device(ctx.handle, TARGETS[name], 0, None, None, None) == _lib.OK  # a no-op
+        ctx.uastc_transcode_rects_device(TARGETS[name], [])
+        torch.cuda.synchronize()
+        surf.check(untouched=True)
+        ctx.uastc_transcode_rects_device(TARGETS[name], good)  # and the same table, unharmed, works
+        torch.cuda.synchronize()
+        surf.check()
+
+
+@pytest.mark.parametrize("name", ["bc7", "etc1", "rgba"])
+def test_a_three_job_call_is_captured_into_a_graph_and_replayed(ctx, slices, name):
+    """the call only enqueues: recorded by stream capture (the pattern of tests/test_gpu_round4.py), replayed twice into re-poisoned surfaces"""
+    import torch
+
+    surf = Surfaces(name, [(slices[k], x0, y0, w, h, pitches(name, w)["padded"], 5000 * k) for k, (x0, y0, w, h) in enumerate(RECTS[2:5])])
+    st = status_word()
+    side = torch.cuda.Stream()
+    table = surf.table()
+
+    def record():
+        ctx.status_word_reset(st, stream=side)
+        ctx.uastc_transcode_rects_device(TARGETS[name], table, d_status=st, stream=side)
+
+    with torch.cuda.stream(side):
+        record()  # (first use outside the capture)
+    torch.cuda.synchronize()
+    surf.check()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        record()
+    del table  # (the job array travelled in the kernel arguments: nothing of it is read at replay)
+    first = None
+    for _ in range(2):
+        surf.poison()
+        st.fill_(0)
+        graph.replay()
+        torch.cuda.synchronize()
+        surf.check()
+        assert word_of(st) == CLEAR
+        got = [surf.arena.data(i).cpu().numpy().copy() for i in range(3)]
+        if first is None:
+            first = got
+        assert all(np.array_equal(a, b) for a, b in zip(first, got))
+
+
+@pytest.mark.parametrize("name", list(TARGETS))
+def test_one_job_over_a_whole_slice_equals_the_plain_launch(ctx, golden, name):
+    import torch
+
+    from basisu_rs_amd import synth
+
+    nbx, nby = 128, 32
+    blocks = np.ascontiguousarray(golden["uastc"][synth.gold_indices(nbx * nby, seed=4711)])
+    blocks[17 * nbx + 5, 0] = BAD_MODE
+    d_in = torch.from_numpy(blocks.reshape(-1)).cuda()
+    t, rb = TARGETS[name], row_bytes(name)
+    n_out = nbx * nby * _lib.BLOCK_BYTES[t]
+    plain = torch.full((n_out,), POISON, dtype=torch.uint8, device="cuda")
+    rects = torch.full((n_out,), POISON, dtype=torch.uint8, device="cuda")
+    st_a, st_b = status_word(), status_word()
+    ctx.status_word_reset(st_a)
+    ctx.status_word_reset(st_b)
+    ctx.transcode_device(t, d_in, nbx * nby, plain, nbx, 77, st_a)
+    ctx.uastc_transcode_rects_device(t, [(d_in, nbx, 0, 0, nbx, nby, rects, nbx * rb, 77)], d_status=st_b)
+    torch.cuda.synchronize()
+    assert torch.equal(plain, rects)
+    assert word_of(st_a) == word_of(st_b) == (77 + 17 * nbx + 5) << 8 | _lib.ERR_INVALID_MODE
