@@ -4,7 +4,10 @@ The test slice is 200 x 40 blocks, block i = known-answer vector i mod 608: ever
 reference's known answers (tests/golden/uastc_kat.bin) for ASTC / BC7 / ETC1 / ETC2 / RGBA32 and bu_uastc_transcode_device over the whole slice -- which its
 own tests pin -- for the six other targets.  Every surface is pre-filled with a poison byte and sits between guard bands (tests/gpu_guard.py): every position
 of a rectangle is compared, every other byte must still be poison, and the slices sit between bands of invalid blocks, so a lane that took a block outside
-its slice would report it."""
+its slice would report it.
+
+No launch of this file holds more tiles than the grid: launches whose workgroups walk from tile to tile across jobs, and chosen per-tile mode histograms in
+the rectangle tile shapes, are in tests/test_gpu_rect_walks.py."""
 import os
 import sys
 

@@ -25,13 +25,18 @@ EMUL_EVERY_BLOCK = 300_000  # cases up to this size go through the host build bl
 
 
 # ---- 1. the bookkeeping, restated -------------------------------------------------------------------------------------------------
-def book(keys, wgs, bpt):
+def book(keys, wgs, bpt, mask=None):
     """the sort of one tile of wgs x bpt blocks whose first len(keys) blocks hold sort keys `keys` (0..19), as bu_uastc_sorted_body does it: block l is lane
     l % 64 of wave (l % wgs) / 64 in load l / wgs; a wave ranks all its loads with one add of 64 per load when every load is of a single key and no lane lacks
-    a block, else with one add of 1 per lane.  Run k = the blocks of key k; runs lie back to back in key order and are cut into chunks of up to 64 blocks"""
+    a block, else with one add of 1 per lane.  Run k = the blocks of key k; runs lie back to back in key order and are cut into chunks of up to 64 blocks.
+    mask (a clipped tile of a rectangle): [T] bool, which lanes hold a block -- `keys` then names a key for every lane, and the lanes outside drop theirs"""
     T = wgs * bpt
     k = np.full(T, sc.NO_BLOCK, dtype=np.int64)
-    k[:len(keys)] = keys
+    if mask is None:
+        k[:len(keys)] = keys
+    else:
+        k[mask] = np.asarray(keys)[mask]
+        keys = k[mask]
     hist = np.bincount(k[k < 20], minlength=20)
     first = np.concatenate([[0], np.cumsum(hist)[:-1]])
     chunks = (hist + 63) // 64
