@@ -51,6 +51,15 @@ __device__ __forceinline__ uint4 bu_ld_stream_global(const uint4* p)
     const bu_v4u r = __builtin_nontemporal_load((bu_global_v4u)p);
     return make_uint4(r.x, r.y, r.z, r.w);
 }
+// The scalar-base form (bu_multi_addr.hpp): a wave-uniform 64-bit address plus a 32-bit byte offset per lane.  Written as a byte pointer into the global address
+// space indexed by an unsigned 32-bit value, it compiles to  global_load_dwordx4 v[..], v_off, s[b:b+1] nt  -- no 64-bit vector arithmetic in front of the access.
+typedef const char __attribute__((address_space(1))) * bu_global_bytes;
+__device__ __forceinline__ uint4 bu_ld_stream_global(uint64_t base, uint32_t off)
+{
+    typedef const bu_v4u __attribute__((address_space(1))) * bu_global_v4u;
+    const bu_v4u r = __builtin_nontemporal_load((bu_global_v4u)((bu_global_bytes)base + off));
+    return make_uint4(r.x, r.y, r.z, r.w);
+}
 // (the compiler's own stores below say "global" for the same reason: every output lies in device memory, and in the multi-run kernels nothing else says so)
 typedef bu_v4u __attribute__((address_space(1))) * bu_global_out_v4u;
 typedef bu_v2u __attribute__((address_space(1))) * bu_global_out_v2u;
@@ -94,6 +103,30 @@ __device__ __forceinline__ void bu_st_stream(uint2* p, const uint2 v)
     *(bu_global_out_v2u)p = r;
 #else
     __builtin_nontemporal_store(r, (bu_global_out_v2u)p);
+#endif
+}
+// The same two stores in the scalar-base form of the multi-run layouts: wave-uniform base, 32-bit byte offset per lane; each in its own cache policy.
+typedef char __attribute__((address_space(1))) * bu_global_out_bytes;
+__device__ __forceinline__ void bu_st_stream(uint64_t base, uint32_t off, const uint4 v)
+{
+    bu_v4u r;
+    r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
+#if BU_ST_MODE == 0
+    __builtin_nontemporal_store(r, (bu_global_out_v4u)((bu_global_out_bytes)base + off));
+#elif BU_ST_MODE == 1
+    *(bu_global_out_v4u)((bu_global_out_bytes)base + off) = r;
+#else
+    asm volatile("global_store_dwordx4 %0, %1, %2" BU_ST_BITS "\n\ts_nop 1" ::"v"(off), "v"(r), "s"(base) : "memory");  // (the s_nop: as above)
+#endif
+}
+__device__ __forceinline__ void bu_st_stream(uint64_t base, uint32_t off, const uint2 v)
+{
+    bu_v2u r;
+    r.x = v.x; r.y = v.y;
+#if BU_ST_MODE == 1
+    *(bu_global_out_v2u)((bu_global_out_bytes)base + off) = r;
+#else
+    __builtin_nontemporal_store(r, (bu_global_out_v2u)((bu_global_out_bytes)base + off));
 #endif
 }
 
@@ -199,15 +232,37 @@ struct BuRunTable {
     uint32_t first_tile[BU_MULTI_RUNS + 32];  // ascending; entries past the last run hold 0xFFFFFFFF (128 entries: two 64-lane loads)
 };
 static_assert(sizeof(BuRunDesc) == 32 && sizeof(BuRunTable) <= 3968, "the run table must fit the 4 KiB of kernel arguments beside the other parameters");
-// the tile the kernel is working on: its run's addresses, where it starts inside the run, how many blocks it holds
+// the tile a one-slice kernel is working on: the launch's addresses (MULTI: BuMultiTile -- the tile, the run being walked and every address derived from
+// them: bu_multi_addr.hpp)
 struct BuTileDesc {
     const uint4* in;
     void* out;
-    uint32_t first;   // strips: the tile's first block inside its run; rectangles: (16 * tile row) * width + 64 * tile column, the block index of the tile's corner
+    uint32_t first;
     uint32_t n;
     uint64_t base;
-    uint32_t width;   // rectangles: blocks per row of the run's (virtual) grid; 0: strips
+    uint32_t width;
 };
+// What a workgroup of the MULTI layouts carries from tile to tile beside the blocks (bu_multi_addr.hpp); empty in every other layout, so that the one-slice and
+// rectangle kernels compile to what they were.
+//   d / l: the tile being sorted, transcoded and written back / the tile being loaded (what `td` / `tl` are to the one-slice layouts)
+//   off: the 32-bit byte offsets of this thread's BPT blocks from the corner of `l`.  They hang on the thread and the run's width alone and are computed anew only
+//     where the walk reaches a run of another width (`off_width`: the width they were computed for) -- never per tile, never per access.  `d` uses the same ones
+//     for its stores, except in the one tile per change of width in which `l` is already in the next run (bu_uastc_sorted_body, store_offsets)
+//   cur: the run of the tile last looked up, in uniform registers.  The next tile lies in the same run nearly every time (a 2^20-block run is 1024 tiles): its
+//     descriptor is then scalar arithmetic on `cur`, with no LDS read, no ballot and no readfirstlane between the scatter and the prefetch loads
+template <bool MULTI, int BPT>
+struct BuMultiWalk {
+    BuMultiTile d = {}, l = {};
+    uint32_t off[BPT] = {};
+    uint32_t off_width = 0xFFFFFFFFu;  // (no run has this width)
+    BuRunCursor cur = bu_no_run();
+};
+template <int BPT>
+struct BuMultiWalk<false, BPT> {};
+template <int BPT>
+__device__ __forceinline__ uint32_t bu_walk_n(const BuMultiWalk<true, BPT>& w) { return w.d.n; }  // blocks of the tile being sorted
+template <int BPT>
+__device__ __forceinline__ uint32_t bu_walk_n(const BuMultiWalk<false, BPT>&) { return 0u; }
 enum { BU_LAYOUT_STRIP = 0, BU_LAYOUT_RECT = 1, BU_LAYOUT_MULTI = 2,
        BU_LAYOUT_MULTI_WHOLE = 3,    // MULTI with every run tiled as whole rectangles (BuRunDesc::vshift): no lane ever lacks a block, and the validity tests fold away as in RECT
        BU_LAYOUT_RECTS = 4 };        // several RECTANGLES cut out of slices, each stored at a pitch of its own (bu_uastc_rects_kernel below; table and address mapping: bu_rect_plan.hpp)
@@ -318,6 +373,10 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // `td` = the descriptor of the tile being sorted / transcoded / written back; `tl` = the descriptor of the tile whose blocks are being
     // LOADED (the same tile, or with PREFETCH the next one: its loads are in flight while `td`'s tile is transcoded)
     BuTileDesc td = {in, out, 0u, 0u, base, 0u}, tl = td;
+    // MULTI: every access of a tile is a wave-uniform 64-bit base (the tile's corner: mw.d.in / mw.d.out, scalar arithmetic per tile) plus the lane's 32-bit byte
+    // offset from that corner (mw.off)
+    BuMultiWalk<MULTI, BPT> mw;
+    constexpr uint32_t OUT_BYTES = TARGET == BU_TGT_RGBA ? 16u : (uint32_t)bu_out_words(TARGET) * 4u;  // bytes of one result store
     // MULTI, persistent grid: the run table is copied to LDS once per workgroup (3.9 KiB) and every later look-up reads it there.  From the kernel
     // arguments a look-up is two vector loads, a ballot and dependent scalar loads -- a microsecond of round trips between the scatter and the prefetch
     // loads of EVERY tile, with the workgroup waiting at barrier (2) behind it (8 % of a multi-run launch over 2^20-block slices)
@@ -333,33 +392,34 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     }
     auto uni32 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
     auto uni64 = [&](uint64_t x) { return (uint64_t)uni32((uint32_t)x) | ((uint64_t)uni32((uint32_t)(x >> 32)) << 32); };
-    auto desc_of = [&](unsigned t, BuTileDesc& d) {
+    auto desc_of = [&](unsigned t, BuMultiTile& d) {
         if constexpr (MULTI) {
             if (t < n_tiles) {
-                // runs 0..r start at or before tile t: r = (number of first-tile entries <= t) - 1; the unused entries are ~0
-                uint32_t r = 0;
+                if (!bu_cursor_holds(mw.cur, t)) {
+                    // runs 0..r start at or before tile t: r = (number of first-tile entries <= t) - 1; the unused entries are ~0
+                    uint32_t r = 0;
+                    // (this path is rare: the lane's address into the first-tile numbers is formed HERE, from a value the compiler cannot trace back to `lane`, or it
+                    //  is hoisted out of the tile loop and holds a register -- in the 64-VGPR kernels a spill slot -- for the whole walk)
+                    uint32_t ln = lane;
+                    asm volatile("" : "+v"(ln));
 #pragma unroll
-                for (unsigned c = 0; c < BU_MULTI_RUNS + 32; c += 64) {
-                    const uint32_t cnt = (uint32_t)__popcll(__ballot(R->first_tile[c + lane] <= t));
-                    if (cnt) r = c + cnt - 1u;
+                    for (unsigned c = 0; c < BU_MULTI_RUNS + 32; c += 64) {
+                        const uint32_t cnt = (uint32_t)__popcll(__ballot(R->first_tile[c + ln] <= t));
+                        if (cnt) r = c + cnt - 1u;
+                    }
+                    r = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
+                    // (the record comes back in vector registers -- an LDS read --, but every lane read the same one: made scalar here, so that everything derived
+                    //  from it is scalar too.  The pointers are rebuilt from integers, so the compiler no longer knows their address space either: the block loads say
+                    //  "global" themselves (bu_ld_stream_global), the result stores are asm global stores in any case)
+                    const BuRunDesc rv = R->run[r];
+                    const BuRunRec rd = {uni64(reinterpret_cast<uint64_t>(rv.in)), uni64(reinterpret_cast<uint64_t>(rv.out)), uni64(rv.base), uni32(rv.n), uni32(rv.vshift)};
+                    mw.cur = bu_run_cursor(rd, uni32(R->first_tile[r]), (uint32_t)BU_TILE);
                 }
-                r = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
-                // (the record comes back in vector registers -- an LDS read --, but every lane read the same one: made scalar here, so that the tile's addresses
-                //  are a wave-uniform 64-bit base.  That is all it buys: every load and store still adds its lane offset to that base with 64-bit VECTOR arithmetic
-                //  (v_lshl_add_u64, then `off`) -- the SGPR-base + 32-bit-offset form of the one-slice kernels does not come out of it, a lane offset times 16 does not
-                //  provably fit 32 bits.  The pointers are rebuilt from integers, so the compiler no longer knows their address space either: the block loads say
-                //  "global" themselves (bu_ld_stream_global), the result stores are asm global stores in any case)
-                const BuRunDesc rv = R->run[r];
-                const BuRunDesc rd = {reinterpret_cast<const uint4*>(uni64(reinterpret_cast<uint64_t>(rv.in))), reinterpret_cast<void*>(uni64(reinterpret_cast<uint64_t>(rv.out))),
-                                      uni64(rv.base), uni32(rv.n), uni32(rv.vshift)};
-                const uint32_t lt = t - uni32(R->first_tile[r]);  // the tile's number inside its run
-                if (rd.vshift != BU_RUN_STRIPS) {
-                    // a 64 x 16-block rectangle of the run's grid (tiles per row a power of two): 16 segments of 1 KiB at the grid's pitch instead of 16 KiB in a row
-                    const uint32_t ty = lt >> rd.vshift, tx = lt & ((1u << rd.vshift) - 1u), width = (uint32_t)BU_RECT_W << rd.vshift;
-                    d = BuTileDesc{rd.in, rd.out, (uint32_t)(BU_TILE / BU_RECT_W) * ty * width + (uint32_t)BU_RECT_W * tx, (uint32_t)BU_TILE, rd.base, width};
-                } else {
-                    const uint32_t first = lt * (uint32_t)BU_TILE, left = rd.n - first;
-                    d = BuTileDesc{rd.in, rd.out, first, left < (uint32_t)BU_TILE ? left : (uint32_t)BU_TILE, rd.base, 0u};
+                d = bu_tile_of(mw.cur, t, (uint32_t)BU_TILE, OUT_BYTES, TARGET == BU_TGT_RGBA ? bpr : 0u);
+                if (d.width != mw.off_width) {  // (uniform: the walk has reached a run of another width)
+                    mw.off_width = d.width;
+#pragma unroll
+                    for (int j = 0; j < BPT; j++) mw.off[j] = bu_lane_off(WHOLE, d.width, (unsigned)(j * WGS) + tid);
                 }
             }
         }
@@ -377,18 +437,34 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             }
         }
     };
-    desc_of(tile, td);
+    if constexpr (MULTI) desc_of(tile, mw.d);
+    if constexpr (MULTI) mw.l = mw.d;
     tl = td;
     rect_of(tile, qd);
     ql = qd;
     // block l of tile t (whose descriptor is `tl`): where it is loaded from, whether it exists
-    // MULTI: block l of the tile described by d, as an index inside d's run (strips: consecutive; rectangles: row l / 64, column l % 64 of the tile)
-    auto run_idx = [&](const BuTileDesc& d, unsigned l) { return d.first + ((WHOLE || d.width) ? (l / BU_RECT_W) * d.width + (l % BU_RECT_W) : l); };
-    auto blk_src = [&](unsigned t, unsigned l) { return RECTS ? reinterpret_cast<const uint4*>(bu_rect_src(ql, l)) : MULTI ? tl.in + run_idx(tl, l) : in + gidx(t, l); };
-    auto ld_blk = [&](unsigned t, unsigned l) { return (MULTI || RECTS) ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
+    // MULTI: block j * WGS + tid of the tile described by mw.l lies mw.off[j] bytes behind the tile's corner
+    auto blk_src = [&](unsigned t, unsigned l) { return RECTS ? reinterpret_cast<const uint4*>(bu_rect_src(ql, l)) : in + gidx(t, l); };
+    auto ld_one = [&](unsigned t, unsigned l) { return RECTS ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
+    auto ld_blk = [&](unsigned t, unsigned l, int j) {  // (l = j * WGS + tid)
+        if constexpr (MULTI) return bu_ld_stream_global(mw.l.in, mw.off[j]);
+        else return ld_one(t, l);
+    };
+    // MULTI: the offsets of the tile being written back.  With PREFETCH the look-up for the next tile has already run: if that tile lies in a run of another width,
+    // mw.off belongs to it, and this tile's offsets are computed once more (a uniform branch, taken once per change of width)
+    auto store_offsets = [&](uint32_t (&so)[MULTI ? BPT : 1]) {
+        if constexpr (MULTI) {
+#pragma unroll
+            for (int j = 0; j < BPT; j++) so[j] = mw.off[j];
+            if (mw.d.width != mw.off_width) {
+#pragma unroll
+                for (int j = 0; j < BPT; j++) so[j] = bu_lane_off(WHOLE, mw.d.width, (unsigned)(j * WGS) + tid);
+            }
+        }
+    };
     auto blk_valid = [&](unsigned t, unsigned l) {
         if constexpr (RECTS) return t < n_tiles && bu_rect_has(ql, l);
-        else if constexpr (MULTI) return t < n_tiles && (WHOLE || l < tl.n);
+        else if constexpr (MULTI) return t < n_tiles && (WHOLE || l < mw.l.n);
         else return RECT ? t < n_tiles : (t < n_tiles && gidx(t, l) < n_blocks && in_tile(l));
     };
     // Table staging.  The staged 16-byte pieces of the LDS image are numbered 0..TVT-1: BC7's own tables, then the target's one or
@@ -415,7 +491,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     uint4 v[BU_BPT];
 #pragma unroll
     for (int j = 0; j < BU_BPT; j++)
-        v[j] = (RECT || blk_valid(tile, j * BU_WG + tid)) ? ld_blk(tile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);  // (RECT: the grid is at most n_tiles)
+        v[j] = (RECT || blk_valid(tile, j * BU_WG + tid)) ? ld_blk(tile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);  // (RECT: the grid is at most n_tiles)
     if constexpr (!SPLIT) {
 #pragma unroll
         for (int k = 0; k < TVN; k++) {
@@ -451,13 +527,13 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // The multi-run kernels run as one-tile workgroups only between one tile per CU and one grid of tiles (bu_plan_multi_kernel).
     constexpr bool STORES_LAST = PREFETCH && MULTI && (TARGET == BU_TGT_BC7 || (TARGET == BU_TGT_ASTC && WGS == 256 && WHOLE));
     // STORES_LAST: sort key of block l of the tile described by d whose first word is x
-    auto key_of = [&](const BuTileDesc& d, unsigned l, uint32_t x) { return (WHOLE || l < d.n) ? (uint32_t)T.key_lut[bu_cost_row(TARGET)][x & 127u] : 31u; };
+    auto key_of = [&](const BuMultiTile& d, unsigned l, uint32_t x) { return (WHOLE || l < d.n) ? (uint32_t)T.key_lut[bu_cost_row(TARGET)][x & 127u] : 31u; };
     uint32_t next_key[STORES_LAST ? BU_BPT : 1];  // STORES_LAST: the keys of the tile about to be sorted, taken in phase D of the tile before it
     uint32_t drawn_tile = 0;  // thread 0, STORES_LAST: tile_of_draw(my_draw), taken before the stores went out
     if constexpr (STORES_LAST) {
         if (tile < n_tiles) {
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(td, j * BU_WG + tid, v[j].x);
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(mw.d, j * BU_WG + tid, v[j].x);
         }
         if (ticket && tid == 0) drawn_tile = tile_of_draw(my_draw);
         // Nothing of the prologue is still in flight here in practice (the table pieces were stored to LDS before the barrier above, the first tile's keys and the first
@@ -481,7 +557,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             if constexpr (STORES_LAST) {
                 key[j] = next_key[j];
             } else {
-                const bool valid = WHOLE || (RECTS ? bu_rect_has(qd, (unsigned)(j * BU_WG) + tid) : MULTI ? (unsigned)(j * BU_WG) + tid < td.n : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
+                const bool valid = WHOLE || (RECTS ? bu_rect_has(qd, (unsigned)(j * BU_WG) + tid) : MULTI ? (unsigned)(j * BU_WG) + tid < bu_walk_n(mw) : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
                 key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
             }
             uniform = uniform && (__ballot(key[j] == (uint32_t)__builtin_amdgcn_readfirstlane(key[j])) == ~0ull) && has_block(key[j]);
@@ -529,11 +605,22 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         next_of_loop = ntile;
         uint4 vn[BU_BPT];
         if constexpr (PREFETCH) {
-            desc_of(ntile, tl);
+            if constexpr (MULTI) desc_of(ntile, mw.l);
             rect_of(ntile, ql);
+            if constexpr (MULTI && WHOLE) {
+                // every lane of every tile has a block: the loads hang on the one uniform condition and issue back to back under it
+                if (ntile < n_tiles) {
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) {
-                vn[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
+                    for (int j = 0; j < BU_BPT; j++) vn[j] = ld_blk(ntile, j * BU_WG + tid, j);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < BU_BPT; j++) vn[j] = make_uint4(0, 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < BU_BPT; j++) {
+                    vn[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);
+                }
             }
         }
         if (ticket && tid == 0 && ntile < n_tiles) my_draw = atomicAdd(my_counter, 1u);  // (for the tile after the next: needed one tile from now)
@@ -592,14 +679,15 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         if constexpr (STORES_LAST) {
             uint4 r[BU_BPT];
             bool has[BU_BPT];
-            auto out_idx = [&](int j) { return run_idx(td, j * BU_WG + tid); };  // (inside the tile's slice)
+            uint32_t so[BU_BPT];
+            store_offsets(so);
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) {
                 has[j] = has_block(key[j]);
                 if (has[j]) {
                     r[j] = sblk[dest[j]];
                     if ((r[j].x & 0xFFu) == 0u) {  // no valid block of these formats starts with a zero byte: word 3 is the status
-                        bu_report(status, td.base + out_idx(j), (int)r[j].w);
+                        bu_report(status, mw.d.base + bu_lane_block(mw.d, so[j]), (int)r[j].w);
                         r[j].w = 0;
                     }
                 }
@@ -609,15 +697,17 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
             // (on EVERY path, needed or not -- behind the last tile `vn` is zeros and the draw is stale: the compiler's wait-count bookkeeping is path-insensitive,
             //  and a use under a condition would leave "may still be pending" standing, to be waited for at the next write to these registers: behind the stores)
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(tl, j * BU_WG + tid, vn[j].x);
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(mw.l, j * BU_WG + tid, vn[j].x);
             drawn_tile = tile_of_draw(my_draw);   // (every lane, with or without tickets: thread 0's is the one that counts, and only under tickets.  These few
                                                   //  instructions and the key look-ups of a zero `vn` behind a workgroup's last tile are work done to steer the
                                                   //  wait-count pass; tests/test_multi_kernel_address_space.py holds what they buy)
             asm volatile("" : "+v"(drawn_tile));  // (plain arithmetic: pinned in front of the stores by hand)
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++)
-                if (has[j]) bu_st_stream(reinterpret_cast<uint4*>(td.out) + out_idx(j), r[j]);
+                if (has[j]) bu_st_stream(mw.d.out, so[j], r[j]);
         } else {
+        [[maybe_unused]] uint32_t so[MULTI ? BU_BPT : 1];
+        store_offsets(so);
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
             if constexpr (RECTS) {  // the three write-back forms at the job's pitch: 16-byte blocks, 8-byte blocks, RGBA32's four pixel rows
@@ -647,9 +737,35 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
                 }
                 continue;
             }
+            if constexpr (MULTI) {  // the same write-back forms from the tile's corner: uniform base, the lane's offset
+                if (has_block(key[j])) {
+                    const uint32_t lo = so[j];
+                    if constexpr (INBLOCK) {
+                        uint4 r = sblk[dest[j]];
+                        if ((r.x & 0xFFu) == 0u) {  // (as below)
+                            bu_report(status, mw.d.base + bu_lane_block(mw.d, lo), (int)r.w);
+                            r.w = 0;
+                        }
+                        bu_st_stream(mw.d.out, lo, r);
+                    } else {
+                        const uint32_t st = sst[dest[j]];
+                        if (st) bu_report(status, mw.d.base + bu_lane_block(mw.d, lo), (int)st);
+                        if constexpr (TARGET == BU_TGT_RGBA) {
+                            const uint32_t row0 = bu_lane_off_rgba(mw.d, lo, bpr);
+#pragma unroll
+                            for (int r = 0; r < 4; r++) bu_st_stream(mw.d.out, row0 + (uint32_t)r * bpr * 16u, sout[r * BU_TILE + dest[j]]);
+                        } else {
+                            const uint4 r = sblk[dest[j]];
+                            if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(mw.d.out, lo >> 1, make_uint2(r.x, r.y));
+                            else bu_st_stream(mw.d.out, lo, r);
+                        }
+                    }
+                }
+                continue;
+            }
             if (has_block(key[j])) {
-                const unsigned idx = MULTI ? run_idx(td, j * BU_WG + tid) : gidx(tile, j * BU_WG + tid);  // (MULTI: inside the tile's slice)
-                void* const out = td.out;                  // (the launch's `out` unless MULTI)
+                const unsigned idx = gidx(tile, j * BU_WG + tid);
+                void* const out = td.out;                  // (the launch's `out`)
                 const unsigned long long base = td.base;
                 if constexpr (INBLOCK) {
                     uint4 r = sblk[dest[j]];
@@ -689,14 +805,16 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) v[j] = vn[j];
             td = tl;
+            if constexpr (MULTI) mw.d = mw.l;
             qd = ql;
         } else {
-            desc_of(ntile, tl);
+            if constexpr (MULTI) desc_of(ntile, mw.l);
+            if constexpr (MULTI) mw.d = mw.l;
             td = tl;
             rect_of(ntile, ql);
             qd = ql;
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid) : make_uint4(0, 0, 0, 0);
+            for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);
         }
         // no barrier here: the next tile's scatter into `sblk` sits behind its barrier (1), which every wave reaches only
         // after its reads of this tile's results have completed

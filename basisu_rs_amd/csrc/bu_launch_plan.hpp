@@ -20,6 +20,12 @@ constexpr bool bu_dyn_tile(int target, int tile) { return bu_etc_family(target) 
 constexpr unsigned BU_RECT_W = 64;  // width of a rectangular tile (bu_kernels.hpp, layout RECT)
 constexpr unsigned BU_MULTI_RUNS = 96;  // runs per multi-run launch (bu_kernels.hpp, BuRunTable)
 constexpr uint32_t BU_RUN_STRIPS = 0xFFFFFFFFu;
+// The widest grid a run of a multi-run launch is tiled on as rectangles (bu_plan_runs).  The kernel keeps a lane's distance from its tile's corner as a 32-bit byte
+// offset: at most (31 rows x this width + 63 blocks) x 16 bytes < 2^29 (bu_multi_addr.hpp asserts it)
+constexpr size_t BU_MULTI_MAX_WIDTH = (size_t)1 << 20;
+// RGBA32: the widest image (blocks per row) whose runs share a multi-run launch -- there the lane offset spans pixel rows of the image (bu_lane_off_rgba);
+// runs of wider images go out one by one as plain launches
+constexpr size_t BU_MULTI_RGBA_MAX_BPR = (size_t)1 << 24;
 // a launch that draws its tiles by ticket needs a grid of at least this many workgroups: the kernel numbers its tiles off eight counters
 constexpr unsigned BU_TICKET_MIN_GRID = 8;
 
@@ -315,7 +321,7 @@ inline void bu_plan_runs(int kernel_target, const BuRun* runs, size_t n_runs, si
     // whole PREFIX goes out as an entry of its own, the remainder as strips -- RGBA32 only: 64 ragged images of 1021 x 1024 blocks 15.0 -> 13.1 us per image, BC7 / ASTC unmoved:
     // profiles/r06_ab_rgba_multi_run_rectangles.txt)
     const bool rect_target = target == BU_TGT_BC7 || target == BU_TGT_ASTC || target == BU_TGT_RGBA;
-    const size_t real = (blocks_per_row >= 128 && (blocks_per_row & (blocks_per_row - 1)) == 0 && blocks_per_row <= ((size_t)1 << 20)) ? blocks_per_row : 0;
+    const size_t real = (blocks_per_row >= 128 && (blocks_per_row & (blocks_per_row - 1)) == 0 && blocks_per_row <= BU_MULTI_MAX_WIDTH) ? blocks_per_row : 0;
     const size_t virt = target == BU_TGT_RGBA ? 0 : 1;
     const size_t pitches[5] = {real, virt * 1024, virt * 2048, virt * 512, virt * 256};
     auto shift_of = [](size_t v) {
@@ -324,6 +330,10 @@ inline void bu_plan_runs(int kernel_target, const BuRun* runs, size_t n_runs, si
         return sh;
     };
     for (size_t r0 = 0; r0 < n_runs;) {
+        if (target == BU_TGT_RGBA && blocks_per_row > BU_MULTI_RGBA_MAX_BPR) {  // (the kernel's 32-bit lane offsets: bu_multi_addr.hpp)
+            out.emplace_back().plain_run = r0++;
+            continue;
+        }
         BuRunsLaunch l;
         // ETC1 / ETC2 batches of 2^20 blocks or more in runs long enough for them: 2048-block tiles, ONE tile per workgroup, dealt by the hardware dispatcher (512 x 4 under the
         // shared shape's launch bounds, two resident per CU) -- what the plain launch does from 2^20 blocks on (bu_plan_slice): 64 slices of 2^20 blocks in separate
