@@ -27,6 +27,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 

@@ -232,37 +232,28 @@ struct BuRunTable {
     uint32_t first_tile[BU_MULTI_RUNS + 32];  // ascending; entries past the last run hold 0xFFFFFFFF (128 entries: two 64-lane loads)
 };
 static_assert(sizeof(BuRunDesc) == 32 && sizeof(BuRunTable) <= 3968, "the run table must fit the 4 KiB of kernel arguments beside the other parameters");
-// the tile a one-slice kernel is working on: the launch's addresses (MULTI: BuMultiTile -- the tile, the run being walked and every address derived from
-// them: bu_multi_addr.hpp)
-struct BuTileDesc {
-    const uint4* in;
-    void* out;
-    uint32_t first;
-    uint32_t n;
-    uint64_t base;
-    uint32_t width;
+// What a workgroup carries from tile to tile beside the blocks: `d` describes the tile being sorted, transcoded and written back, `l` the tile whose blocks are being
+// LOADED (the same tile, or with PREFETCH the next one: its loads are in flight while `d`'s tile is transcoded).
+//   one slice (STRIP, RECT): nothing.  A tile is its number and every address hangs on the launch's `in` / `out` / `base`, so these kernels carry nothing of the other
+//     layouts' and compile to what they were
+//   RECTS: BuRectTile, the tile's corner in its job's slice and surface (bu_rect_plan.hpp)
+//   MULTI: BuMultiTile -- the tile, the run being walked and every address derived from them (bu_multi_addr.hpp) -- and beside the two tiles
+//     off: the 32-bit byte offsets of this thread's BPT blocks from the corner of `l`.  They hang on the thread and the run's width alone and are computed anew only
+//       where the walk reaches a run of another width (`off_width`: the width they were computed for) -- never per tile, never per access.  `d` uses the same ones
+//       for its stores, except in the one tile per change of width in which `l` is already in the next run (bu_uastc_sorted_body, `so`)
+//     cur: the run of the tile last looked up, in uniform registers.  The next tile lies in the same run nearly every time (a 2^20-block run is 1024 tiles): its
+//       descriptor is then scalar arithmetic on `cur`, with no LDS read, no ballot and no readfirstlane between the scatter and the prefetch loads
+struct BuNoTile {};
+template <class TILE>
+struct BuWalk {
+    TILE d = {}, l = {};
 };
-// What a workgroup of the MULTI layouts carries from tile to tile beside the blocks (bu_multi_addr.hpp); empty in every other layout, so that the one-slice and
-// rectangle kernels compile to what they were.
-//   d / l: the tile being sorted, transcoded and written back / the tile being loaded (what `td` / `tl` are to the one-slice layouts)
-//   off: the 32-bit byte offsets of this thread's BPT blocks from the corner of `l`.  They hang on the thread and the run's width alone and are computed anew only
-//     where the walk reaches a run of another width (`off_width`: the width they were computed for) -- never per tile, never per access.  `d` uses the same ones
-//     for its stores, except in the one tile per change of width in which `l` is already in the next run (bu_uastc_sorted_body, store_offsets)
-//   cur: the run of the tile last looked up, in uniform registers.  The next tile lies in the same run nearly every time (a 2^20-block run is 1024 tiles): its
-//     descriptor is then scalar arithmetic on `cur`, with no LDS read, no ballot and no readfirstlane between the scatter and the prefetch loads
-template <bool MULTI, int BPT>
-struct BuMultiWalk {
-    BuMultiTile d = {}, l = {};
+template <int BPT>
+struct BuMultiWalk : BuWalk<BuMultiTile> {
     uint32_t off[BPT] = {};
     uint32_t off_width = 0xFFFFFFFFu;  // (no run has this width)
     BuRunCursor cur = bu_no_run();
 };
-template <int BPT>
-struct BuMultiWalk<false, BPT> {};
-template <int BPT>
-__device__ __forceinline__ uint32_t bu_walk_n(const BuMultiWalk<true, BPT>& w) { return w.d.n; }  // blocks of the tile being sorted
-template <int BPT>
-__device__ __forceinline__ uint32_t bu_walk_n(const BuMultiWalk<false, BPT>&) { return 0u; }
 enum { BU_LAYOUT_STRIP = 0, BU_LAYOUT_RECT = 1, BU_LAYOUT_MULTI = 2,
        BU_LAYOUT_MULTI_WHOLE = 3,    // MULTI with every run tiled as whole rectangles (BuRunDesc::vshift): no lane ever lacks a block, and the validity tests fold away as in RECT
        BU_LAYOUT_RECTS = 4 };        // several RECTANGLES cut out of slices, each stored at a pitch of its own (bu_uastc_rects_kernel below; table and address mapping: bu_rect_plan.hpp)
@@ -369,13 +360,11 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     unsigned* const my_counter = ticket ? ticket + (blockIdx.x & 7u) * BU_TICKET_STRIDE : nullptr;
     auto tile_of_draw = [&](uint32_t d) { return gridDim.x + 8u * d + (blockIdx.x & 7u); };
     if (ticket && tid == 0) my_draw = atomicAdd(my_counter, 1u);
-    // MULTI: the current tile's descriptor (wave-uniform: scalar loads); every other layout addresses the one slice of the launch
-    // `td` = the descriptor of the tile being sorted / transcoded / written back; `tl` = the descriptor of the tile whose blocks are being
-    // LOADED (the same tile, or with PREFETCH the next one: its loads are in flight while `td`'s tile is transcoded)
-    BuTileDesc td = {in, out, 0u, 0u, base, 0u}, tl = td;
-    // MULTI: every access of a tile is a wave-uniform 64-bit base (the tile's corner: mw.d.in / mw.d.out, scalar arithmetic per tile) plus the lane's 32-bit byte
-    // offset from that corner (mw.off)
-    BuMultiWalk<MULTI, BPT> mw;
+    // w.d / w.l: the tile being sorted, transcoded and written back / the tile being loaded (BuWalk; wave-uniform: scalar).  The one-slice layouts have no descriptor.
+    // MULTI: every access of a tile is a wave-uniform 64-bit base (the tile's corner: w.d.in / w.d.out, scalar arithmetic per tile) plus the lane's 32-bit byte
+    // offset from that corner (w.off)
+    using Tile = std::conditional_t<MULTI, BuMultiTile, std::conditional_t<RECTS, BuRectTile, BuNoTile>>;
+    std::conditional_t<MULTI, BuMultiWalk<BPT>, BuWalk<Tile>> w;
     constexpr uint32_t OUT_BYTES = TARGET == BU_TGT_RGBA ? 16u : (uint32_t)bu_out_words(TARGET) * 4u;  // bytes of one result store
     // MULTI, persistent grid: the run table is copied to LDS once per workgroup (3.9 KiB) and every later look-up reads it there.  From the kernel
     // arguments a look-up is two vector loads, a ballot and dependent scalar loads -- a microsecond of round trips between the scatter and the prefetch
@@ -392,10 +381,11 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     }
     auto uni32 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
     auto uni64 = [&](uint64_t x) { return (uint64_t)uni32((uint32_t)x) | ((uint64_t)uni32((uint32_t)(x >> 32)) << 32); };
-    auto desc_of = [&](unsigned t, BuMultiTile& d) {
+    // the descriptor of tile t into w.l (nothing behind the last tile, nothing at all in the one-slice layouts)
+    auto look_up = [&](unsigned t) {
         if constexpr (MULTI) {
             if (t < n_tiles) {
-                if (!bu_cursor_holds(mw.cur, t)) {
+                if (!bu_cursor_holds(w.cur, t)) {
                     // runs 0..r start at or before tile t: r = (number of first-tile entries <= t) - 1; the unused entries are ~0
                     uint32_t r = 0;
                     // (this path is rare: the lane's address into the first-tile numbers is formed HERE, from a value the compiler cannot trace back to `lane`, or it
@@ -413,60 +403,44 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
                     //  "global" themselves (bu_ld_stream_global), the result stores are asm global stores in any case)
                     const BuRunDesc rv = R->run[r];
                     const BuRunRec rd = {uni64(reinterpret_cast<uint64_t>(rv.in)), uni64(reinterpret_cast<uint64_t>(rv.out)), uni64(rv.base), uni32(rv.n), uni32(rv.vshift)};
-                    mw.cur = bu_run_cursor(rd, uni32(R->first_tile[r]), (uint32_t)BU_TILE);
+                    w.cur = bu_run_cursor(rd, uni32(R->first_tile[r]), (uint32_t)BU_TILE);
                 }
-                d = bu_tile_of(mw.cur, t, (uint32_t)BU_TILE, OUT_BYTES, TARGET == BU_TGT_RGBA ? bpr : 0u);
-                if (d.width != mw.off_width) {  // (uniform: the walk has reached a run of another width)
-                    mw.off_width = d.width;
+                w.l = bu_tile_of(w.cur, t, (uint32_t)BU_TILE, OUT_BYTES, TARGET == BU_TGT_RGBA ? bpr : 0u);
+                if (w.l.width != w.off_width) {  // (uniform: the walk has reached a run of another width)
+                    w.off_width = w.l.width;
 #pragma unroll
-                    for (int j = 0; j < BPT; j++) mw.off[j] = bu_lane_off(WHOLE, d.width, (unsigned)(j * WGS) + tid);
+                    for (int j = 0; j < BPT; j++) w.off[j] = bu_lane_off(WHOLE, w.l.width, (unsigned)(j * WGS) + tid);
                 }
             }
-        }
-    };
-    // RECTS: `qd` / `ql` are what `td` / `tl` are to MULTI; tile t belongs to the last job whose first tile is <= t (first_tile[0] = 0: there is one)
-    BuRectTile qd = {}, ql = {};
-    auto rect_of = [&](unsigned t, BuRectTile& d) {
-        if constexpr (RECTS) {
+        } else if constexpr (RECTS) {  // tile t belongs to the last job whose first tile is <= t (first_tile[0] = 0: there is one)
             if (t < n_tiles) {
                 static_assert(BU_RECT_JOBS == 64, "one first-tile number per lane");
                 const uint32_t r = uni32((uint32_t)__popcll(__ballot(Q->first_tile[lane] <= t)) - 1u);
                 const BuRectDesc jv = Q->job[r];  // (every lane reads the same record: made scalar, as MULTI's)
                 const BuRectDesc jd = {uni64(jv.in), uni64(jv.out), uni64(jv.pitch), uni64(jv.base), uni32(jv.in_bpr), uni32(jv.w), uni32(jv.h), uni32(jv.tpr)};
-                d = bu_rect_tile(jd, t - uni32(Q->first_tile[r]), RECTS_ROW_BYTES, RECTS_ROWS);
+                w.l = bu_rect_tile(jd, t - uni32(Q->first_tile[r]), RECTS_ROW_BYTES, RECTS_ROWS);
             }
         }
     };
-    if constexpr (MULTI) desc_of(tile, mw.d);
-    if constexpr (MULTI) mw.l = mw.d;
-    tl = td;
-    rect_of(tile, qd);
-    ql = qd;
-    // block l of tile t (whose descriptor is `tl`): where it is loaded from, whether it exists
-    // MULTI: block j * WGS + tid of the tile described by mw.l lies mw.off[j] bytes behind the tile's corner
-    auto blk_src = [&](unsigned t, unsigned l) { return RECTS ? reinterpret_cast<const uint4*>(bu_rect_src(ql, l)) : in + gidx(t, l); };
-    auto ld_one = [&](unsigned t, unsigned l) { return RECTS ? bu_ld_stream_global(blk_src(t, l)) : bu_ld_stream(blk_src(t, l)); };  // (one slice: `in` is a kernel argument, global already)
-    auto ld_blk = [&](unsigned t, unsigned l, int j) {  // (l = j * WGS + tid)
-        if constexpr (MULTI) return bu_ld_stream_global(mw.l.in, mw.off[j]);
-        else return ld_one(t, l);
+    auto advance = [&] { w.d = w.l; };  // the tile that was loaded is the one to sort
+    look_up(tile);
+    advance();
+    // has block l of tile t, described by d, a block?  (WHOLE: every lane of every tile has one, and the validity tests fold away)
+    auto has_blk = [&](const Tile& d, unsigned t, unsigned l) {
+        if constexpr (WHOLE) return true;
+        else if constexpr (RECTS) return bu_rect_has(d, l);
+        else if constexpr (MULTI) return l < d.n;
+        else return t * tile_blocks + l < n_blocks && in_tile(l);
     };
-    // MULTI: the offsets of the tile being written back.  With PREFETCH the look-up for the next tile has already run: if that tile lies in a run of another width,
-    // mw.off belongs to it, and this tile's offsets are computed once more (a uniform branch, taken once per change of width)
-    auto store_offsets = [&](uint32_t (&so)[MULTI ? BPT : 1]) {
-        if constexpr (MULTI) {
-#pragma unroll
-            for (int j = 0; j < BPT; j++) so[j] = mw.off[j];
-            if (mw.d.width != mw.off_width) {
-#pragma unroll
-                for (int j = 0; j < BPT; j++) so[j] = bu_lane_off(WHOLE, mw.d.width, (unsigned)(j * WGS) + tid);
-            }
-        }
+    // block j * WGS + tid of tile t, the tile described by w.l, loaded (MULTI: it lies w.off[j] bytes behind the tile's corner; one slice: `in` is a kernel
+    // argument, global already); ld_or_zero: zeros where the lane has none or the walk has ended
+    auto ld_blk = [&](unsigned t, int j) {
+        if constexpr (MULTI) return bu_ld_stream_global(w.l.in, w.off[j]);
+        else if constexpr (RECTS) return bu_ld_stream_global(reinterpret_cast<const uint4*>(bu_rect_src(w.l, (unsigned)(j * WGS) + tid)));
+        else return bu_ld_stream(in + gidx(t, (unsigned)(j * WGS) + tid));
     };
-    auto blk_valid = [&](unsigned t, unsigned l) {
-        if constexpr (RECTS) return t < n_tiles && bu_rect_has(ql, l);
-        else if constexpr (MULTI) return t < n_tiles && (WHOLE || l < mw.l.n);
-        else return RECT ? t < n_tiles : (t < n_tiles && gidx(t, l) < n_blocks && in_tile(l));
-    };
+    // (`&`, not `&&`: one lane mask per load, no uniform branch around each of them)
+    auto ld_or_zero = [&](unsigned t, int j) { return ((t < n_tiles) & has_blk(w.l, t, (unsigned)(j * WGS) + tid)) ? ld_blk(t, j) : make_uint4(0, 0, 0, 0); };
     // Table staging.  The staged 16-byte pieces of the LDS image are numbered 0..TVT-1: BC7's own tables, then the target's one or
     // two ranges of the common blob; piece i sits at t_store[tdst(i)] and comes from the same index of the image's source in device
     // memory.  Every thread issues ALL its table loads back to back (round 2 ran a load / wait / store loop: a second L2 round
@@ -490,8 +464,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     }
     uint4 v[BU_BPT];
 #pragma unroll
-    for (int j = 0; j < BU_BPT; j++)
-        v[j] = (RECT || blk_valid(tile, j * BU_WG + tid)) ? ld_blk(tile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);  // (RECT: the grid is at most n_tiles)
+    for (int j = 0; j < BU_BPT; j++) v[j] = RECT ? ld_blk(tile, j) : ld_or_zero(tile, j);  // (RECT: the grid is at most n_tiles)
     if constexpr (!SPLIT) {
 #pragma unroll
         for (int k = 0; k < TVN; k++) {
@@ -526,14 +499,14 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
     // have no next tile and pay for this order (results out of LDS first, keys of an empty `vn`) in front of their only stores: 8.41 -> 8.61 us per 2^20-block atlas.
     // The multi-run kernels run as one-tile workgroups only between one tile per CU and one grid of tiles (bu_plan_multi_kernel).
     constexpr bool STORES_LAST = PREFETCH && MULTI && (TARGET == BU_TGT_BC7 || (TARGET == BU_TGT_ASTC && WGS == 256 && WHOLE));
-    // STORES_LAST: sort key of block l of the tile described by d whose first word is x
-    auto key_of = [&](const BuMultiTile& d, unsigned l, uint32_t x) { return (WHOLE || l < d.n) ? (uint32_t)T.key_lut[bu_cost_row(TARGET)][x & 127u] : 31u; };
+    // sort key of thread block j of tile t, described by d, whose first word is x: the position of its mode in BU_COST_ORDER; 31 where the lane has no block
+    auto key_of = [&](const Tile& d, unsigned t, int j, uint32_t x) { return has_blk(d, t, (unsigned)(j * BU_WG) + tid) ? (uint32_t)T.key_lut[bu_cost_row(TARGET)][x & 127u] : 31u; };
     uint32_t next_key[STORES_LAST ? BU_BPT : 1];  // STORES_LAST: the keys of the tile about to be sorted, taken in phase D of the tile before it
     uint32_t drawn_tile = 0;  // thread 0, STORES_LAST: tile_of_draw(my_draw), taken before the stores went out
     if constexpr (STORES_LAST) {
         if (tile < n_tiles) {
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(mw.d, j * BU_WG + tid, v[j].x);
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(w.d, tile, j, v[j].x);
         }
         if (ticket && tid == 0) drawn_tile = tile_of_draw(my_draw);
         // Nothing of the prologue is still in flight here in practice (the table pieces were stored to LDS before the barrier above, the first tile's keys and the first
@@ -543,7 +516,6 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         __builtin_amdgcn_s_waitcnt(0x0F70);
     }
     for (; tile < n_tiles; tile = next_of_loop, par ^= 1u) {
-        [[maybe_unused]] const unsigned tbase = tile * tile_blocks;
         // ---- A: sort key + rank within the key (counting sort, pass 1) ----
         // key = position of the block's mode in BU_COST_ORDER (runs are laid out heaviest code path first).
         // Rank within the key = one LDS atomic per block.  64 lanes adding to ONE counter serialise, though, and that is
@@ -554,12 +526,7 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         bool uniform = true;
 #pragma unroll
         for (int j = 0; j < BU_BPT; j++) {
-            if constexpr (STORES_LAST) {
-                key[j] = next_key[j];
-            } else {
-                const bool valid = WHOLE || (RECTS ? bu_rect_has(qd, (unsigned)(j * BU_WG) + tid) : MULTI ? (unsigned)(j * BU_WG) + tid < bu_walk_n(mw) : (tbase + j * BU_WG + tid < n_blocks && in_tile(j * BU_WG + tid)));  // (RECT: whole tiles only)
-                key[j] = valid ? T.key_lut[bu_cost_row(TARGET)][v[j].x & 127u] : 31u;
-            }
+            key[j] = STORES_LAST ? next_key[j] : key_of(w.d, tile, j, v[j].x);
             uniform = uniform && (__ballot(key[j] == (uint32_t)__builtin_amdgcn_readfirstlane(key[j])) == ~0ull) && has_block(key[j]);
         }
         if (uniform) {
@@ -605,22 +572,19 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         next_of_loop = ntile;
         uint4 vn[BU_BPT];
         if constexpr (PREFETCH) {
-            if constexpr (MULTI) desc_of(ntile, mw.l);
-            rect_of(ntile, ql);
+            look_up(ntile);
             if constexpr (MULTI && WHOLE) {
                 // every lane of every tile has a block: the loads hang on the one uniform condition and issue back to back under it
                 if (ntile < n_tiles) {
 #pragma unroll
-                    for (int j = 0; j < BU_BPT; j++) vn[j] = ld_blk(ntile, j * BU_WG + tid, j);
+                    for (int j = 0; j < BU_BPT; j++) vn[j] = ld_blk(ntile, j);
                 } else {
 #pragma unroll
                     for (int j = 0; j < BU_BPT; j++) vn[j] = make_uint4(0, 0, 0, 0);
                 }
             } else {
 #pragma unroll
-                for (int j = 0; j < BU_BPT; j++) {
-                    vn[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);
-                }
+                for (int j = 0; j < BU_BPT; j++) vn[j] = ld_or_zero(ntile, j);
             }
         }
         if (ticket && tid == 0 && ntile < n_tiles) my_draw = atomicAdd(my_counter, 1u);  // (for the tile after the next: needed one tile from now)
@@ -676,146 +640,114 @@ __device__ __forceinline__ void bu_uastc_sorted_body(const uint4* __restrict__ i
         }
         __syncthreads();  // (3) every result is in LDS
         // ---- D: results leave in original order ----
+        // MULTI: the lane offsets of the tile being written back.  With PREFETCH the look-up for the next tile has already run: if that tile lies in a run of another
+        // width, w.off belongs to it, and this tile's offsets are computed once more (a uniform branch, taken once per change of width)
+        [[maybe_unused]] uint32_t so[MULTI ? BU_BPT : 1];
+        if constexpr (MULTI) {
+#pragma unroll
+            for (int j = 0; j < BPT; j++) so[j] = w.off[j];
+            if (w.d.width != w.off_width) {
+#pragma unroll
+                for (int j = 0; j < BPT; j++) so[j] = bu_lane_off(WHOLE, w.d.width, (unsigned)(j * WGS) + tid);
+            }
+        }
+        // The layouts differ in which block of the call thread block j is (status words) and in where its result goes -- 16 bytes, 8 bytes, or pixel row r of RGBA32's
+        // four: at the job's pitch (RECTS), from the tile's corner by the lane's offset (MULTI), by the block's index in the slice (one slice)
+        auto blk_of = [&](int j) -> unsigned long long {
+            if constexpr (RECTS) return w.d.base + bu_rect_idx(w.d, (unsigned)(j * BU_WG) + tid);
+            else if constexpr (MULTI) return w.d.base + bu_lane_block(w.d, so[j]);
+            else return base + gidx(tile, (unsigned)(j * BU_WG) + tid);
+        };
+        auto put16 = [&](int j, const uint4 r) {
+            if constexpr (RECTS) bu_st_stream(reinterpret_cast<uint4*>(bu_rect_dst(w.d, (unsigned)(j * BU_WG) + tid, RECTS_ROW_BYTES, RECTS_ROWS)), r);
+            else if constexpr (MULTI) bu_st_stream(w.d.out, so[j], r);
+            else bu_st_stream(reinterpret_cast<uint4*>(out) + gidx(tile, (unsigned)(j * BU_WG) + tid), r);
+        };
+        auto put8 = [&](int j, const uint2 r) {
+            if constexpr (RECTS) bu_st_stream(reinterpret_cast<uint2*>(bu_rect_dst(w.d, (unsigned)(j * BU_WG) + tid, RECTS_ROW_BYTES, RECTS_ROWS)), r);
+            else if constexpr (MULTI) bu_st_stream(w.d.out, so[j] >> 1, r);
+            else bu_st_stream(reinterpret_cast<uint2*>(out) + gidx(tile, (unsigned)(j * BU_WG) + tid), r);
+        };
+        auto put_row = [&](int j, int r, const uint4 px) {
+            const unsigned l = (unsigned)(j * BU_WG) + tid;
+            if constexpr (RECTS) {
+                bu_st_stream(reinterpret_cast<uint4*>(bu_rect_dst(w.d, l, RECTS_ROW_BYTES, RECTS_ROWS) + (uint64_t)r * w.d.pitch), px);
+            } else if constexpr (MULTI) {
+                bu_st_stream(w.d.out, bu_lane_off_rgba(w.d, so[j], bpr) + (uint32_t)r * bpr * 16u, px);
+            } else {
+                unsigned by, bx;
+                if constexpr (RECT) {  // block row and column straight from the tile coordinates: no division
+                    unsigned ty, tx;
+                    tile_xy(tile, ty, tx);
+                    by = (unsigned)(BU_TILE / BU_RECT_W) * ty + l / BU_RECT_W;
+                    bx = BU_RECT_W * tx + (l % BU_RECT_W);
+                } else {
+                    by = gidx(tile, l) / bpr;
+                    bx = gidx(tile, l) - by * bpr;
+                }
+                bu_st_stream(reinterpret_cast<uint4*>(out) + (size_t)((4 * by + r) * bpr + bx), px);
+            }
+        };
+        // BC7, ASTC: thread block j's result out of its slot; no valid block of these formats starts with a zero byte: word 3 is then the status, reported and cleared
+        auto take_inblock = [&](int j) {
+            uint4 r = sblk[dest[j]];
+            if ((r.x & 0xFFu) == 0u) {
+                bu_report(status, blk_of(j), (int)r.w);
+                r.w = 0;
+            }
+            return r;
+        };
         if constexpr (STORES_LAST) {
             uint4 r[BU_BPT];
             bool has[BU_BPT];
-            uint32_t so[BU_BPT];
-            store_offsets(so);
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) {
                 has[j] = has_block(key[j]);
-                if (has[j]) {
-                    r[j] = sblk[dest[j]];
-                    if ((r[j].x & 0xFFu) == 0u) {  // no valid block of these formats starts with a zero byte: word 3 is the status
-                        bu_report(status, mw.d.base + bu_lane_block(mw.d, so[j]), (int)r[j].w);
-                        r[j].w = 0;
-                    }
-                }
+                if (has[j]) r[j] = take_inblock(j);
             }
             // everything this wave still has in flight is consumed HERE, in front of the stores (the asm stores clobber memory: the LDS reads of key_lut stay
             // on this side of them, and so does the compiler's wait for `vn`)
             // (on EVERY path, needed or not -- behind the last tile `vn` is zeros and the draw is stale: the compiler's wait-count bookkeeping is path-insensitive,
             //  and a use under a condition would leave "may still be pending" standing, to be waited for at the next write to these registers: behind the stores)
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(mw.l, j * BU_WG + tid, vn[j].x);
+            for (int j = 0; j < BU_BPT; j++) next_key[j] = key_of(w.l, ntile, j, vn[j].x);
             drawn_tile = tile_of_draw(my_draw);   // (every lane, with or without tickets: thread 0's is the one that counts, and only under tickets.  These few
                                                   //  instructions and the key look-ups of a zero `vn` behind a workgroup's last tile are work done to steer the
                                                   //  wait-count pass; tests/test_multi_kernel_address_space.py holds what they buy)
             asm volatile("" : "+v"(drawn_tile));  // (plain arithmetic: pinned in front of the stores by hand)
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++)
-                if (has[j]) bu_st_stream(mw.d.out, so[j], r[j]);
+                if (has[j]) put16(j, r[j]);
         } else {
-        [[maybe_unused]] uint32_t so[MULTI ? BU_BPT : 1];
-        store_offsets(so);
 #pragma unroll
-        for (int j = 0; j < BU_BPT; j++) {
-            if constexpr (RECTS) {  // the three write-back forms at the job's pitch: 16-byte blocks, 8-byte blocks, RGBA32's four pixel rows
-                if (has_block(key[j])) {
-                    const unsigned l = j * BU_WG + tid;
-                    const unsigned long long blk = qd.base + bu_rect_idx(qd, l);
-                    const uint64_t dst = bu_rect_dst(qd, l, RECTS_ROW_BYTES, RECTS_ROWS);
-                    if constexpr (INBLOCK) {
-                        uint4 r = sblk[dest[j]];
-                        if ((r.x & 0xFFu) == 0u) {  // (as below)
-                            bu_report(status, blk, (int)r.w);
-                            r.w = 0;
-                        }
-                        bu_st_stream(reinterpret_cast<uint4*>(dst), r);
-                    } else {
-                        const uint32_t st = sst[dest[j]];
-                        if (st) bu_report(status, blk, (int)st);
-                        if constexpr (TARGET == BU_TGT_RGBA) {
-#pragma unroll
-                            for (int r = 0; r < 4; r++) bu_st_stream(reinterpret_cast<uint4*>(dst + (uint64_t)r * qd.pitch), sout[r * BU_TILE + dest[j]]);
-                        } else {
-                            const uint4 r = sblk[dest[j]];
-                            if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(dst), make_uint2(r.x, r.y));
-                            else bu_st_stream(reinterpret_cast<uint4*>(dst), r);
-                        }
-                    }
-                }
-                continue;
-            }
-            if constexpr (MULTI) {  // the same write-back forms from the tile's corner: uniform base, the lane's offset
-                if (has_block(key[j])) {
-                    const uint32_t lo = so[j];
-                    if constexpr (INBLOCK) {
-                        uint4 r = sblk[dest[j]];
-                        if ((r.x & 0xFFu) == 0u) {  // (as below)
-                            bu_report(status, mw.d.base + bu_lane_block(mw.d, lo), (int)r.w);
-                            r.w = 0;
-                        }
-                        bu_st_stream(mw.d.out, lo, r);
-                    } else {
-                        const uint32_t st = sst[dest[j]];
-                        if (st) bu_report(status, mw.d.base + bu_lane_block(mw.d, lo), (int)st);
-                        if constexpr (TARGET == BU_TGT_RGBA) {
-                            const uint32_t row0 = bu_lane_off_rgba(mw.d, lo, bpr);
-#pragma unroll
-                            for (int r = 0; r < 4; r++) bu_st_stream(mw.d.out, row0 + (uint32_t)r * bpr * 16u, sout[r * BU_TILE + dest[j]]);
-                        } else {
-                            const uint4 r = sblk[dest[j]];
-                            if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(mw.d.out, lo >> 1, make_uint2(r.x, r.y));
-                            else bu_st_stream(mw.d.out, lo, r);
-                        }
-                    }
-                }
-                continue;
-            }
-            if (has_block(key[j])) {
-                const unsigned idx = gidx(tile, j * BU_WG + tid);
-                void* const out = td.out;                  // (the launch's `out`)
-                const unsigned long long base = td.base;
+            for (int j = 0; j < BU_BPT; j++) {
+                if (!has_block(key[j])) continue;
                 if constexpr (INBLOCK) {
-                    uint4 r = sblk[dest[j]];
-                    if ((r.x & 0xFFu) == 0u) {  // no valid block of these formats starts with a zero byte: word 3 is the status
-                        bu_report(status, base + idx, (int)r.w);
-                        r.w = 0;
-                    }
-                    bu_st_stream(reinterpret_cast<uint4*>(out) + idx, r);
-                    continue;
-                }
-                const uint32_t st = sst[dest[j]];
-                if (st) bu_report(status, base + idx, (int)st);
-                if constexpr (TARGET == BU_TGT_RGBA) {
-                    unsigned by, bx;
-                    if constexpr (RECT) {  // block row and column straight from the tile coordinates: no division
-                        const unsigned l = j * BU_WG + tid;
-                        unsigned ty, tx;
-                        tile_xy(tile, ty, tx);
-                        by = (unsigned)(BU_TILE / BU_RECT_W) * ty + l / BU_RECT_W;
-                        bx = BU_RECT_W * tx + (l % BU_RECT_W);
-                    } else {
-                        by = idx / bpr;
-                        bx = idx - by * bpr;
-                    }
-                    uint4* img = reinterpret_cast<uint4*>(out);
-#pragma unroll
-                    for (int r = 0; r < 4; r++) bu_st_stream(img + (size_t)((4 * by + r) * bpr + bx), sout[r * BU_TILE + dest[j]]);
+                    put16(j, take_inblock(j));
                 } else {
-                    const uint4 r = sblk[dest[j]];
-                    if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out) + idx, make_uint2(r.x, r.y));
-                    else bu_st_stream(reinterpret_cast<uint4*>(out) + idx, r);
+                    const uint32_t st = sst[dest[j]];
+                    if (st) bu_report(status, blk_of(j), (int)st);
+                    if constexpr (TARGET == BU_TGT_RGBA) {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) put_row(j, r, sout[r * BU_TILE + dest[j]]);
+                    } else {
+                        const uint4 r = sblk[dest[j]];
+                        if constexpr (bu_out_words(TARGET) == 2) put8(j, make_uint2(r.x, r.y));
+                        else put16(j, r);
+                    }
                 }
             }
         }
-        }
+        // the tile that has been loaded -- ahead of time with PREFETCH, only now without -- becomes the tile to sort
         if constexpr (PREFETCH) {
 #pragma unroll
             for (int j = 0; j < BU_BPT; j++) v[j] = vn[j];
-            td = tl;
-            if constexpr (MULTI) mw.d = mw.l;
-            qd = ql;
         } else {
-            if constexpr (MULTI) desc_of(ntile, mw.l);
-            if constexpr (MULTI) mw.d = mw.l;
-            td = tl;
-            rect_of(ntile, ql);
-            qd = ql;
+            look_up(ntile);
 #pragma unroll
-            for (int j = 0; j < BU_BPT; j++) v[j] = blk_valid(ntile, j * BU_WG + tid) ? ld_blk(ntile, j * BU_WG + tid, j) : make_uint4(0, 0, 0, 0);
+            for (int j = 0; j < BU_BPT; j++) v[j] = ld_or_zero(ntile, j);
         }
+        advance();
         // no barrier here: the next tile's scatter into `sblk` sits behind its barrier (1), which every wave reaches only
         // after its reads of this tile's results have completed
     }
