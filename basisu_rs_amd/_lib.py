@@ -24,7 +24,7 @@ SYMBOLS = [
     "bu_transcode_uastc_block_to_etc1", "bu_transcode_uastc_block_to_etc2", "bu_block_api_on_device", "bu_context_set_launch_policy", "bu_context_get_launch_policy", "bu_context_stream", "bu_context_synchronize", "bu_context_probe_streams", "bu_context_query_in_flight", "bu_uastc_transcode_device_sync",
     "bu_uastc_transcode_device", "bu_uastc_transcode_batch_device", "bu_uastc_transcode_batch_in_flight", "bu_uastc_transcode_rects_device", "bu_status_word_reset", "bu_status_word_decode", "bu_host_alloc", "bu_host_free",
     "bu_etc1s_selector_from_rows", "bu_etc1s_transcode_etc1_device", "bu_etc1s_decode_rgba_device",
-    "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode",
+    "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode", "bu_etc1s_transcode_rects_device",
     "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_read_file_query", "bu_read_file_to", "bu_basislz_decode",
     "bu_basis_write_uastc",
     "bu_comm_unique_id", "bu_comm_create", "bu_comm_destroy", "bu_comm_query", "bu_allgather_inplace",
@@ -68,6 +68,12 @@ class ImageDesc(ctypes.Structure):  # bu_image
 class RectJob(ctypes.Structure):  # bu_rect_job
     _fields_ = [("d_in", ctypes.c_void_p), ("in_blocks_per_row", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32),
                 ("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("d_out", ctypes.c_void_p), ("out_pitch_bytes", ctypes.c_uint64),
+                ("index_base", ctypes.c_uint64)]
+
+
+class Etc1sRectJob(ctypes.Structure):  # bu_etc1s_rect_job
+    _fields_ = [("d_idx", ctypes.c_void_p), ("d_alpha_idx", ctypes.c_void_p), ("in_blocks_per_row", ctypes.c_uint32), ("x0", ctypes.c_uint32),
+                ("y0", ctypes.c_uint32), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("d_out", ctypes.c_void_p), ("out_pitch_bytes", ctypes.c_uint64),
                 ("index_base", ctypes.c_uint64)]
 
 
@@ -152,6 +158,9 @@ def load():
     lib.bu_etc1s_transcode_device.restype = c.c_int
     lib.bu_etc1s_transcode.argtypes = [vp, c.c_int, vp, vp, sz, vp, u32, vp, u32, vp, sz, u64p]
     lib.bu_etc1s_transcode.restype = c.c_int
+    if hasattr(lib, "bu_etc1s_transcode_rects_device"):  # (an older build under BASISU_HIP_LIB, for an A/B, lacks it: calling it there raises)
+        lib.bu_etc1s_transcode_rects_device.argtypes = [vp, c.c_int, sz, c.POINTER(Etc1sRectJob), vp, u32, vp, u32, vp, vp]
+        lib.bu_etc1s_transcode_rects_device.restype = c.c_int
     szp = c.POINTER(sz)
     lib.bu_basis_read_header.argtypes = [vp, sz, c.POINTER(BasisHeader)]
     lib.bu_basis_read_header.restype = c.c_int

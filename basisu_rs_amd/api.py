@@ -234,6 +234,22 @@ class Context:
                                                  _stream_ptr(stream))
         self._check(st)
 
+    def etc1s_transcode_rects_device(self, fmt, jobs, d_endpoints, n_endpoints, d_selectors, n_selectors, d_status=None, stream=None):
+        """bu_etc1s_transcode_rects_device: rectangles of ETC1S slices (one codebook pair) into pitched surfaces, all in one call; only enqueues.  fmt: ETC1,
+        RGBA32 or one of the six targets of etc1s_transcode.  jobs: a sequence of (d_idx, d_alpha_idx | None, in_blocks_per_row, x0, y0, w, h, d_out,
+        out_pitch_bytes[, index_base]) -- the pointers device tensors or raw pointers -- or _lib.Etc1sRectJob"""
+        arr = (_lib.Etc1sRectJob * len(jobs))()
+        for i, j in enumerate(jobs):
+            if isinstance(j, _lib.Etc1sRectJob):
+                arr[i] = j
+                continue
+            d_idx, d_aidx, bpr, x0, y0, w, h, d_out, pitch = j[:9]
+            arr[i] = _lib.Etc1sRectJob(_ptr(d_idx).value, None if d_aidx is None else _ptr(d_aidx).value, int(bpr), int(x0), int(y0), int(w), int(h),
+                                       _ptr(d_out).value, int(pitch), int(j[9]) if len(j) > 9 else 0)
+        st = self._lib.bu_etc1s_transcode_rects_device(self._h, int(fmt), len(jobs), arr if len(jobs) else None, _ptr(d_endpoints), int(n_endpoints),
+                                                       _ptr(d_selectors), int(n_selectors), _ptr(d_status), _stream_ptr(stream))
+        self._check(st)
+
     # ---- device-pointer API (torch tensors or raw pointers) ---------------------------------------
     def transcode_device(self, fmt, d_in, n_blocks, d_out, blocks_per_row=0, block_index_base=0, d_status=None, stream=None):
         st = self._lib.bu_uastc_transcode_device(self._h, int(fmt), _ptr(d_in), int(n_blocks), _ptr(d_out), int(blocks_per_row),

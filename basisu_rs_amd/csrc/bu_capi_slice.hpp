@@ -701,6 +701,39 @@ bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uin
     return BU_OK;
 }
 
+// Rectangles of ETC1S slices into pitched surfaces (include/basisu_hip.h): every job is checked before anything is enqueued, then the plan of
+// bu_etc1s_rect_plan.hpp is launched -- the job table in the kernel arguments, nothing allocated, copied or freed behind the call.  One kernel per target, by
+// bu_target value; the gather shape at every size (no LDS-staged form: DESIGN.md section 4.8).
+bu_status bu_etc1s_transcode_rects_device(bu_context* ctx, bu_target target, size_t n_jobs, const bu_etc1s_rect_job* jobs, const uint32_t* d_endpoints,
+                                          uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors, uint64_t* d_status, void* stream)
+{
+    typedef void (*Fn)(const BuEtc1sRectTable, uint32_t, const uint32_t*, uint32_t, const uint2*, uint32_t, unsigned long long*, const BuTablesAll*);
+    static const Fn kernels[BU_N_TARGETS] = {nullptr, nullptr, &bu_etc1s_rects_kernel<BU_TGT_ETC1>, nullptr, &bu_etc1s_rects_kernel<BU_TGT_RGBA>, nullptr,
+                                             &bu_etc1s_rects_kernel<BU_TGT_BC4>, &bu_etc1s_rects_kernel<BU_TGT_BC5>, &bu_etc1s_rects_kernel<BU_TGT_R11>,
+                                             &bu_etc1s_rects_kernel<BU_TGT_RG11>, nullptr, &bu_etc1s_rects_kernel<BU_TGT_BC1>, &bu_etc1s_rects_kernel<BU_TGT_BC3>};
+    if (!ctx || !bu_etc1s_rects_target_ok((int)target) || (n_jobs && !jobs)) return BU_ERR_ARGUMENT;
+    if (n_jobs == 0) return BU_OK;
+    if (!d_endpoints || !d_selectors) return BU_ERR_ARGUMENT;
+    std::vector<BuEtc1sRectJobIn> in(n_jobs);
+    for (size_t i = 0; i < n_jobs; i++) {
+        const bu_etc1s_rect_job& j = jobs[i];
+        in[i] = BuEtc1sRectJobIn{reinterpret_cast<uint64_t>(j.d_idx), reinterpret_cast<uint64_t>(j.d_alpha_idx), j.in_blocks_per_row, j.x0, j.y0, j.w, j.h,
+                                 reinterpret_cast<uint64_t>(j.d_out), j.out_pitch_bytes, j.index_base};
+        if (!bu_etc1s_rect_job_ok((int)target, in[i])) return BU_ERR_ARGUMENT;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    BU_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<BuEtc1sRectsLaunch> plan;
+    bu_plan_etc1s_rects(in.data(), n_jobs, (unsigned)ctx->cu_count, plan);
+    for (const BuEtc1sRectsLaunch& l : plan) {
+        hipLaunchKernelGGL(kernels[target], dim3(l.grid), dim3(l.block), 0, s, l.table, (uint32_t)l.n_units, d_endpoints, n_endpoints,
+                           static_cast<const uint2*>(d_selectors), n_selectors, reinterpret_cast<unsigned long long*>(d_status), ctx->d_tables);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return bu_fail(ctx, e, "ETC1S rectangle launch");
+    }
+    return BU_OK;
+}
+
 // The host-pointer ETC1S calls: stage the indices and both codebooks, launch `target`'s device call (BU_TARGET_ETC1,
 // BU_TARGET_RGBA32 -- nbx x nby blocks -- or one of bu_etc1s_transcode_device's), copy back and synchronise.
 static bu_status bu_etc1s_host(bu_context* ctx, bu_target target, const uint32_t* idx, const uint32_t* alpha_idx, size_t nbx, size_t nby,

@@ -1,4 +1,4 @@
-// The ETC1S back-end kernels: codebook indices -> ETC1, RGBA32 and the six targets of bu_etc1s_targets.hpp, per slice and per file.
+// The ETC1S back-end kernels: codebook indices -> ETC1, RGBA32 and the six targets of bu_etc1s_targets.hpp, per slice, per file and per rectangle.
 // The per-block code (index split and check, ETC1 block, palettes, RGBA32 block, target blocks) is bu_etc1s_targets.hpp's, which
 // the CPU tests compile for the host; this header holds what only the device has: loads, codebook reads, stores and the status word.
 // (Included by bu_hip.hip after bu_kernels.hpp: bu_report, bu_st_stream.)
@@ -332,6 +332,64 @@ __global__ __launch_bounds__(BU_WG) void bu_etc1s_file_target_kernel(const uint3
         }
         if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(out + sd.out_ofs) + i, make_uint2(o[0], o[1]));
         else bu_st_stream(reinterpret_cast<uint4*>(out + sd.out_ofs) + i, make_uint4(o[0], o[1], o[2], o[3]));
+    }
+}
+
+// ---- rectangles of slices into pitched surfaces (bu_etc1s_transcode_rects_device; table, units and address mapping: bu_etc1s_rect_plan.hpp) -------------
+// TARGET: BU_TGT_ETC1, BU_TGT_RGBA or one of the six.  The structure of bu_etc1s_file_target_kernel -- a wave per 64-block unit, the unit number made scalar
+// first, the palette table in LDS (ETC1 needs none), codebooks gathered through the L2, nontemporal index loads -- over the units of the jobs of `table`, a
+// kernel argument: the search for a unit's job and its descriptor are scalar loads from the argument segment.  A lane holds the block of its row and column of
+// the unit (clipped lanes sit out) and stores it at the job's pitch: one store, RGBA32 four.  Every address is rebuilt from the table's integers, so the index
+// loads name the global address space themselves (bu_st_stream does); a job with an alpha slice has its indices checked whether TARGET reads A or not.
+typedef const uint32_t __attribute__((address_space(1))) * bu_global_u32;
+template <int TARGET>
+__global__ __launch_bounds__(BU_WG) void bu_etc1s_rects_kernel(const BuEtc1sRectTable table, uint32_t n_units, const uint32_t* __restrict__ endpoints, uint32_t n_ep,
+                                                               const uint2* __restrict__ selectors, uint32_t n_sel, unsigned long long* status,
+                                                               const BuTablesAll* __restrict__ tables)
+{
+    static_assert(sizeof(BuEtc1sRectTable) + 4 + 4 + 8 + 4 + 4 + 8 + 8 + 8 <= 4096 && BU_ETC1S_RECTS_OTHER_ARGS == 48,
+                  "the job table and the other arguments share the 4 KiB of kernel arguments");
+    constexpr bool ETC1 = TARGET == BU_TGT_ETC1, RGBA = TARGET == BU_TGT_RGBA;
+    constexpr uint32_t ROW_BYTES = bu_rect_row_bytes(TARGET), ROWS = bu_rect_rows_per_block(TARGET);
+    __shared__ uint32_t pal_lut[ETC1 ? 1 : 256];
+    if constexpr (!ETC1) {
+        pal_lut[threadIdx.x] = tables->t.etc1s_pal[threadIdx.x];
+        static_assert(BU_WG == 256, "one palette word per thread");
+        __syncthreads();
+    }
+    const BuEtc1sBooks<false, ETC1> cb = {nullptr, nullptr, endpoints, selectors};
+    const uint32_t lane = threadIdx.x & 63u, wpg = BU_WG / 64;
+    for (uint32_t uv = blockIdx.x * wpg + (threadIdx.x >> 6); uv < n_units; uv += gridDim.x * wpg) {
+        const uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)uv);
+        const uint32_t r = bu_etc1s_rect_unit_job(table.first_unit, unit);
+        const BuEtc1sRectUnit u = bu_etc1s_rect_unit(table.job[r], unit - table.first_unit[r], ROW_BYTES, ROWS);
+        if (!bu_etc1s_rect_has(u, lane)) continue;
+        const uint32_t off = bu_etc1s_rect_idx(u, lane);
+        const unsigned long long i = u.base + off;
+        const uint64_t dst = bu_etc1s_rect_dst(u, lane, ROW_BYTES, ROWS);
+        const uint32_t ix = __builtin_nontemporal_load((bu_global_u32)u.idx + off);
+        if constexpr (ETC1) {
+            bu_st_stream(reinterpret_cast<uint2*>(dst), bu_etc1s_etc1_lane(cb, ix, n_ep, n_sel, status, i));
+        } else {
+            const bool has_a = u.aidx != 0;
+            const uint32_t ax = has_a ? __builtin_nontemporal_load((bu_global_u32)u.aidx + off) : 0u;
+            const BuEtc1sIndex k = bu_etc1s_index(ix, has_a, ax, n_ep, n_sel);
+            uint32_t o[RGBA ? 16 : 4];
+            if (bu_etc1s_good(k, status, i, o)) {
+                uint32_t pr, pg, pb, pa, rows, arows;
+                bu_etc1s_fetch(cb, pal_lut, k, has_a, pr, pg, pb, pa, rows, arows);
+                if constexpr (RGBA) bu_etc1s_block_rgba(pr, pg, pb, pa, rows, has_a, arows, o);
+                else bu_etc1s_target_block<TARGET>(tables->t, pr, pg, pb, rows, has_a, pa, arows, o);
+            }
+            if constexpr (RGBA) {
+#pragma unroll
+                for (int y = 0; y < 4; y++)
+                    bu_st_stream(reinterpret_cast<uint4*>(dst + (uint64_t)y * u.pitch), make_uint4(o[4 * y], o[4 * y + 1], o[4 * y + 2], o[4 * y + 3]));
+            } else {
+                if constexpr (bu_out_words(TARGET) == 2) bu_st_stream(reinterpret_cast<uint2*>(dst), make_uint2(o[0], o[1]));
+                else bu_st_stream(reinterpret_cast<uint4*>(dst), make_uint4(o[0], o[1], o[2], o[3]));
+            }
+        }
     }
 }
 

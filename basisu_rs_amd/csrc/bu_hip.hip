@@ -38,6 +38,7 @@
 #include "bu_etc1s_targets.hpp"   // ETC1S per block: index check, ETC1, RGBA32, BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 (palette form)
 #include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 #include "bu_rect_plan.hpp"    // rectangles of slices into pitched surfaces: job table, address mapping, launch plan
+#include "bu_etc1s_rect_plan.hpp"  // the same for ETC1S slices: 64-block units, a wave each
 #include "bu_multi_addr.hpp"   // the multi-run launch: run cursor, tile corner, lane offsets (one copy for the kernel and the host tests)
 
 #include "bu_kernels.hpp"        // device code: UASTC, status reset, CRC, sleep, copy

@@ -341,6 +341,41 @@ bu_status bu_etc1s_transcode_device(bu_context* ctx, bu_target target, const uin
 bu_status bu_etc1s_transcode(bu_context* ctx, bu_target target, const uint32_t* idx, const uint32_t* alpha_idx, size_t n_blocks,
                              const uint32_t* endpoints, uint32_t n_endpoints, const uint8_t* selectors, uint32_t n_selectors,
                              uint8_t* out, size_t out_bytes, uint64_t* first_bad_block);
+/* RECTANGLES of ETC1S slices into PITCHED surfaces, many in one call: what bu_uastc_transcode_rects_device is to UASTC slices, for the decoded form of an
+ * ETC1S file that a paging system keeps resident (two codebooks and one index word per block) -- 32 x 32-block pages into a page cache, atlas regions, upload
+ * buffers with a row alignment, without a tight scratch buffer and a 2-D copy behind it and without one launch per block row of a page.  All jobs of a call share
+ * the one codebook pair (the pages of one file).
+ *   Targets: BU_TARGET_ETC1, BU_TARGET_RGBA32, BU_TARGET_BC1_RGB, BU_TARGET_BC3_RGBA, BU_TARGET_BC4_R, BU_TARGET_BC5_RG, BU_TARGET_EAC_R11, BU_TARGET_EAC_RG11;
+ *   any other value (ASTC, BC7, ETC2 and the non-targets 5, 10, 13 included) is BU_ERR_ARGUMENT.
+ *   For every job and every 0 <= x < w, 0 <= y < h the bytes written for block (x, y) are exactly what the whole-slice call -- bu_etc1s_transcode_etc1_device
+ *   for ETC1, bu_etc1s_decode_rgba_device with the same alpha array for RGBA32, bu_etc1s_transcode_device for the six -- writes for block
+ *   (y0 + y) * in_blocks_per_row + (x0 + x), a bad block's zeros included.  Block-linear targets write them at d_out + y * out_pitch_bytes + x * block_bytes;
+ *   RGBA32 writes pixel row r of the block (16 bytes) at d_out + (4 y + r) * out_pitch_bytes + 16 x.  No byte outside those positions is written, no index word
+ *   outside a rectangle is read, and a bad index of the slice that lies in no rectangle is never reported.
+ *   d_status (optional): min over the failing blocks of all jobs of (index_base + (y0 + y) * in_blocks_per_row + (x0 + x)) << 8 | BU_ERR_INDEX_RANGE; a job's
+ *   alpha indices are validated whether the target reads A or not, as bu_etc1s_transcode_device does.
+ * Argument rules, all checked for EVERY job before anything is enqueued (BU_ERR_ARGUMENT, nothing launched): jobs non-NULL unless n_jobs == 0 (BU_OK, nothing
+ * done); d_endpoints, d_selectors non-NULL; d_idx, d_out non-NULL; w, h, in_blocks_per_row >= 1; x0 + w <= in_blocks_per_row; (y0 + h) * in_blocks_per_row
+ * <= 2^32; d_idx, and d_alpha_idx if set, 4-byte aligned; d_out and out_pitch_bytes multiples of the row bytes (8 for the 8-byte targets, else 16, RGBA32
+ * included); out_pitch_bytes >= w * row bytes; for BU_TARGET_ETC1 d_alpha_idx must be NULL (ETC1 has no alpha).  Outputs of different jobs must not overlap and
+ * no output may alias an input (the caller's duty, unchecked).
+ * The call only enqueues on `stream`: the job table travels in the kernel arguments (64 jobs per launch; longer lists go out as several launches, in order),
+ * nothing is allocated, copied from the host asynchronously, freed or synchronised behind it, `jobs` may be reused when it returns, and it may be recorded by
+ * stream capture and replayed.  A job is cut into 64-block units, a wave each: 2^k blocks wide (the smallest power of two not below min(w, 64)) and 64 >> k
+ * high, so a 32 x 32-block page is 16 full units and a one-block-wide column fills its lanes. */
+typedef struct bu_etc1s_rect_job {
+    const uint32_t* d_idx;        /* index word of block (0,0) of the SLICE the rectangle is cut from; 4-byte aligned */
+    const uint32_t* d_alpha_idx;  /* the paired alpha slice (same block grid), or NULL: A = 255 */
+    uint32_t in_blocks_per_row;   /* width of the slice's block grid, >= 1 */
+    uint32_t x0, y0;              /* first block column / row of the rectangle inside the slice */
+    uint32_t w, h;                /* blocks, both >= 1; x0 + w <= in_blocks_per_row */
+    void* d_out;                  /* where the rectangle's block (0,0) goes (RGBA32: its pixel (0,0)) */
+    uint64_t out_pitch_bytes;     /* one block row of the output to the next (RGBA32: one PIXEL row to the next) */
+    uint64_t index_base;          /* added to the block's slice index in the status word */
+} bu_etc1s_rect_job;              /* 64 bytes, d_out at offset 40 */
+bu_status bu_etc1s_transcode_rects_device(bu_context* ctx, bu_target target, size_t n_jobs, const bu_etc1s_rect_job* jobs /* HOST array */,
+                                          const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors,
+                                          uint64_t* d_status, void* stream);
 
 /* ---- whole-file level: the crate's public read_to_* API (src/lib.rs:20-22, src/basis.rs) -------------
  * Host side in C++ (container parse, CRC-16, BasisLZ entropy decode -- byte/symbol serial, stays on the CPU),

@@ -116,6 +116,23 @@ pub struct bu_rect_job {
     pub index_base: u64,
 }
 
+/// bu_etc1s_rect_job: one rectangle of an ETC1S slice (index words, optional alpha slice) and the pitched surface it is transcoded into
+/// (bu_etc1s_transcode_rects_device); 64 bytes, d_out at offset 40
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bu_etc1s_rect_job {
+    pub d_idx: *const u32,
+    pub d_alpha_idx: *const u32,
+    pub in_blocks_per_row: u32,
+    pub x0: u32,
+    pub y0: u32,
+    pub w: u32,
+    pub h: u32,
+    pub d_out: *mut c_void,
+    pub out_pitch_bytes: u64,
+    pub index_base: u64,
+}
+
 extern "C" {
     pub fn bu_context_create(device: c_int, out_ctx: *mut *mut bu_context) -> c_int;
     pub fn bu_context_destroy(ctx: *mut bu_context);
@@ -213,4 +230,8 @@ extern "C" {
 extern "C" {
     pub(crate) fn bu_uastc_transcode_rects_device(ctx: *mut bu_context, target: c_int, n_jobs: usize, jobs: *const bu_rect_job, d_status: *mut u64,
                                                   stream: *mut c_void) -> c_int;
+    // the same for ETC1S slices, all jobs over one codebook pair (tests/test_etc1s_rect_capi.py; `etc1s_transcode_rects_device` of lib.rs)
+    pub(crate) fn bu_etc1s_transcode_rects_device(ctx: *mut bu_context, target: c_int, n_jobs: usize, jobs: *const bu_etc1s_rect_job,
+                                                  d_endpoints: *const u32, n_endpoints: u32, d_selectors: *const c_void, n_selectors: u32,
+                                                  d_status: *mut u64, stream: *mut c_void) -> c_int;
 }

@@ -5,8 +5,8 @@
 //!   read_to_rgba / read_to_etc1 / read_to_etc2 / read_to_uastc / read_to_astc / read_to_bc7   (basis.rs:8-260)
 //!   unpack_uastc_block_to_rgba, transcode_uastc_block_to_{astc,bc7,etc1,etc2}                   (lib.rs:29-53)
 //!   Image<T>, Header                                                                            (lib.rs:63-68, basis.rs:417-473)
-//! plus `transcode_array_sharded`, the multi-device entry, and `transcode_rects_device` (rectangles of resident slices into pitched surfaces), which
-//! the reference has no counterparts for.
+//! plus `transcode_array_sharded`, the multi-device entry, and `transcode_rects_device` / `etc1s_transcode_rects_device` (rectangles of resident UASTC / ETC1S
+//! slices into pitched surfaces), which the reference has no counterparts for.
 pub mod ffi;
 
 use std::ffi::CStr;
@@ -205,6 +205,21 @@ pub fn transcode_slice(format: TargetTextureFormat, data: &[u8]) -> Result<Vec<u
 pub unsafe fn transcode_rects_device(ctx: *mut ffi::bu_context, target: c_int, jobs: &[ffi::bu_rect_job], d_status: *mut u64,
                                      stream: *mut core::ffi::c_void) -> Result<()> {
     check(ctx, ffi::bu_uastc_transcode_rects_device(ctx, target, jobs.len(), jobs.as_ptr(), d_status, stream))
+}
+
+/// Rectangles of device-resident ETC1S slices -- index words, optionally a paired alpha slice, one codebook pair for all `jobs` -- into pitched
+/// surfaces in one enqueue on `stream` (bu_etc1s_transcode_rects_device, no counterpart in the reference).  `target` is `ffi::BU_TARGET_ETC1`,
+/// `BU_TARGET_RGBA32` or one of BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11.  Only argument and launch errors are returned; a bad index is reported in
+/// `d_status`.  `jobs` may be dropped when the call returns.
+///
+/// # Safety
+/// `ctx` is a live context; the codebooks hold `n_endpoints` words and `n_selectors` 8-byte entries; every `d_idx` / `d_alpha_idx` / `d_out` of
+/// `jobs` and `d_status` (unless null) are device pointers of its device that cover what the jobs name; outputs overlap neither each other nor an
+/// input; `stream` is null or a stream of that device.
+pub unsafe fn etc1s_transcode_rects_device(ctx: *mut ffi::bu_context, target: c_int, jobs: &[ffi::bu_etc1s_rect_job], d_endpoints: *const u32,
+                                           n_endpoints: u32, d_selectors: *const core::ffi::c_void, n_selectors: u32, d_status: *mut u64,
+                                           stream: *mut core::ffi::c_void) -> Result<()> {
+    check(ctx, ffi::bu_etc1s_transcode_rects_device(ctx, target, jobs.len(), jobs.as_ptr(), d_endpoints, n_endpoints, d_selectors, n_selectors, d_status, stream))
 }
 
 /// Texture array sharded over the devices `devices` of one node (no counterpart in the reference, which walks the slices
