@@ -25,6 +25,7 @@ SYMBOLS = [
     "bu_uastc_transcode_device", "bu_uastc_transcode_batch_device", "bu_uastc_transcode_batch_in_flight", "bu_uastc_transcode_rects_device", "bu_status_word_reset", "bu_status_word_decode", "bu_host_alloc", "bu_host_free",
     "bu_etc1s_selector_from_rows", "bu_etc1s_transcode_etc1_device", "bu_etc1s_decode_rgba_device",
     "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode", "bu_etc1s_transcode_rects_device",
+    "bu_blocks_decode_rgba_device", "bu_blocks_decode_rgba",
     "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_read_file_query", "bu_read_file_to", "bu_basislz_decode",
     "bu_basis_write_uastc",
     "bu_comm_unique_id", "bu_comm_create", "bu_comm_destroy", "bu_comm_query", "bu_allgather_inplace",
@@ -161,6 +162,11 @@ def load():
     if hasattr(lib, "bu_etc1s_transcode_rects_device"):  # (an older build under BASISU_HIP_LIB, for an A/B, lacks it: calling it there raises)
         lib.bu_etc1s_transcode_rects_device.argtypes = [vp, c.c_int, sz, c.POINTER(Etc1sRectJob), vp, u32, vp, u32, vp, vp]
         lib.bu_etc1s_transcode_rects_device.restype = c.c_int
+    if hasattr(lib, "bu_blocks_decode_rgba_device"):  # (an older build under BASISU_HIP_LIB, for an A/B, lacks them: calling them there raises)
+        lib.bu_blocks_decode_rgba_device.argtypes = [vp, c.c_int, vp, sz, vp, sz, sz, c.c_uint64, vp, vp]
+        lib.bu_blocks_decode_rgba_device.restype = c.c_int
+        lib.bu_blocks_decode_rgba.argtypes = [vp, c.c_int, vp, sz, sz, vp, sz, u64p]
+        lib.bu_blocks_decode_rgba.restype = c.c_int
     szp = c.POINTER(sz)
     lib.bu_basis_read_header.argtypes = [vp, sz, c.POINTER(BasisHeader)]
     lib.bu_basis_read_header.restype = c.c_int

@@ -83,13 +83,13 @@ class Context:
     def handle(self):
         return self._h
 
-    def _check(self, st, bad=None):
+    def _check(self, st, bad=None, block_errors=(_lib.ERR_INVALID_MODE, _lib.ERR_INVALID_PATTERN, _lib.ERR_INDEX_RANGE)):
         if st == _lib.OK:
             return
         detail = None
         if st == _lib.ERR_HIP:
             detail = self._lib.bu_last_error(self._h).decode()
-        raise BasisuError(st, bad.value if bad is not None and st in (_lib.ERR_INVALID_MODE, _lib.ERR_INVALID_PATTERN, _lib.ERR_INDEX_RANGE) else None, detail)
+        raise BasisuError(st, bad.value if bad is not None and st in block_errors else None, detail)
 
     # ---- host-pointer slice API -----------------------------------------------------------------
     def host_alloc(self, nbytes):
@@ -130,6 +130,21 @@ class Context:
         bad = ctypes.c_uint64(0)
         st = self._lib.bu_uastc_decode_to_rgba(self._h, a.ctypes.data, a.size, int(blocks_per_row), out.ctypes.data, out.size, ctypes.byref(bad))
         self._check(st, bad)
+        return out[: n * 64]
+
+    _DECODE_BLOCK_ERRORS = (_lib.ERR_INVALID_MODE, _lib.ERR_UNSUPPORTED)  # what a block of decode_blocks can fail with
+
+    def decode_blocks(self, fmt, data, blocks_per_row, out=None):
+        """bu_blocks_decode_rgba: blocks of one of the ten block formats (ASTC, BC7, ETC1, ETC2, BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB, BC3_RGBA)
+        -> the row-major RGBA8 bytes of the image, 4 * blocks_per_row pixels wide.  A block that cannot be decoded raises
+        BasisuError with ERR_INVALID_MODE or ERR_UNSUPPORTED and first_bad_block set; `out` (optional) then holds zeros for every such block."""
+        a = _as_u8(data)
+        n = a.size // _lib.BLOCK_BYTES.get(int(fmt), 16)
+        if out is None:
+            out = np.empty(max(n, 1) * 64, dtype=np.uint8)
+        bad = ctypes.c_uint64(0)
+        st = self._lib.bu_blocks_decode_rgba(self._h, int(fmt), a.ctypes.data, a.size, int(blocks_per_row), out.ctypes.data, out.size, ctypes.byref(bad))
+        self._check(st, bad, self._DECODE_BLOCK_ERRORS)
         return out[: n * 64]
 
     def set_launch_policy(self, shared):
@@ -255,6 +270,13 @@ class Context:
         st = self._lib.bu_uastc_transcode_device(self._h, int(fmt), _ptr(d_in), int(n_blocks), _ptr(d_out), int(blocks_per_row),
                                                  int(block_index_base), _ptr(d_status), _stream_ptr(stream))
         self._check(st)
+
+    def decode_blocks_device(self, fmt, d_blocks, n_blocks, d_rgba, blocks_per_row, out_pitch_bytes=0, block_index_base=0, d_status=None, stream=None):
+        """bu_blocks_decode_rgba_device: the device form of decode_blocks (torch tensors or raw pointers); only enqueues.  out_pitch_bytes = 0: a tight
+        image of 16 * blocks_per_row bytes per pixel row.  Block errors arrive through d_status (status_word_decode)."""
+        st = self._lib.bu_blocks_decode_rgba_device(self._h, int(fmt), _ptr(d_blocks), int(n_blocks), _ptr(d_rgba), int(blocks_per_row), int(out_pitch_bytes),
+                                                    int(block_index_base), _ptr(d_status), _stream_ptr(stream))
+        self._check(st, None, self._DECODE_BLOCK_ERRORS)
 
     def transcode_device_sync(self, fmt, d_in, n_blocks, d_out, blocks_per_row=0, block_index_base=0):
         """bu_uastc_transcode_device_sync: a contiguous device-resident range, blocking; one exclusive launch, tile tickets on long walks.

@@ -160,9 +160,9 @@ bu_status bu_status_word_reset(bu_context* ctx, uint64_t* d_status, void* stream
 bu_status bu_status_word_decode(uint64_t word, uint64_t* first_bad_block)
 {
     if (word == BU_STATUS_WORD_CLEAR) return BU_OK;
-    // a report is (block << 8 | status) with status 1 or 2 (6 for ETC1S): anything else was never reset or was overwritten
+    // a report is (block << 8 | status) with status 1 or 2 (6 for ETC1S; 1 or 17 for the block decoders): anything else was never reset or was overwritten
     const unsigned st = (unsigned)(word & 0xFFu);
-    if (st != BU_ERR_INVALID_MODE && st != BU_ERR_INVALID_PATTERN && st != BU_ERR_INDEX_RANGE) return BU_ERR_ARGUMENT;
+    if (st != BU_ERR_INVALID_MODE && st != BU_ERR_INVALID_PATTERN && st != BU_ERR_INDEX_RANGE && st != BU_ERR_UNSUPPORTED) return BU_ERR_ARGUMENT;
     if (first_bad_block) *first_bad_block = word >> 8;
     return static_cast<bu_status>(st);
 }

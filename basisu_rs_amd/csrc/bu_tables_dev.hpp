@@ -164,11 +164,30 @@ struct BuTables {
     alignas(16) uint32_t etc1s_pal[256];
 };
 static_assert(sizeof(BuTables) % 16 == 0, "BuTables is copied to LDS in 16-byte pieces");
+// The block decoders' tables (bu_decode_blocks.hpp), behind the common blob: only the decode kernels stage them.
+//   [BC7][ASTC]; the ETC / EAC decoders read etc1_mod and eac_mods of BuTables.
+struct BuDecTables {
+    // ---- BC7 ----
+    alignas(16) BuU2 bc7_part[128];  // BPTC partition p: [p] two subsets, [64 + p] three: x = subset of each texel, 2 bits per texel, texel 0 low;
+                                     // y = anchor texel of subset 1 | of subset 2 << 4
+    uint8_t bc7_w[32];               // interpolation weights: index (1 << bits) - 4 + i for bits = 2, 3, 4
+    // ---- ASTC ----
+    alignas(16) uint16_t astc_trit[256];  // trit block T -> its five trits, trit i in bits [2i, 2i + 2) (every one of the 256 values, as the specification decodes them)
+    uint16_t astc_quint[128];             // quint block Q -> its three quints, quint i in bits [3i, 3i + 3)
+    uint8_t astc_rng[24];                 // integer-sequence range r (the 21 of the specification by size): bits | trits << 4 | quints << 5
+    uint16_t astc_cofs[24];               // range r -> offset of its colour unquantisation table in astc_cdeq
+    uint8_t astc_wofs[16];                // weight range r (0..11) -> offset in astc_wdeq
+    uint8_t astc_wdeq[144];               // weight unquantisation, 0..64: index digit << bits | bit value
+    uint8_t astc_cdeq[1216];              // colour unquantisation, 0..255: the same index, all 21 ranges
+};
+static_assert(sizeof(BuDecTables) % 16 == 0 && offsetof(BuDecTables, astc_trit) % 16 == 0, "staged in 16-byte pieces");
 struct BuTablesAll {  // the device blob: one allocation, one kernel argument
     BuBc7Tables b7;
     BuTables t;
+    BuDecTables dec;
 };
 static_assert(offsetof(BuTablesAll, t) == sizeof(BuBc7Tables), "bu_bc7_tables() steps back by sizeof(BuBc7Tables)");
+static_assert(offsetof(BuTablesAll, dec) % 16 == 0, "staged in 16-byte pieces");
 
 // byte ranges [lo, hi) of BuTables a target reads (target ids as in bu_uastc_dispatch.hpp: 0 ASTC, 1 BC7, 2 ETC1, 3 ETC2,
 // 4 RGBA32, 6..9 the channel targets, 11 / 12 BC1 / BC3, which read what RGBA32 reads); a second range is empty unless lo2 < hi2.
@@ -211,6 +230,114 @@ static inline int bu_etc1_bias1_host(int v, int delta, int limit)
     if (v == limit) return v + delta - 1;
     const int m = v + delta;
     return (m < 0 || m > limit) ? v - delta : m;
+}
+
+// ASTC unquantisation of one value of a range with `bits` plain bits and a trit or quint digit (specification, "colour unquantisation" /
+// "weight unquantisation": the A / B / C / D form), m = the bit value
+static inline unsigned bu_astc_unq_colour(int bits, int trits, int quints, unsigned digit, unsigned m)
+{
+    if (!trits && !quints) {
+        unsigned v = 0;
+        for (int s = 8 - bits; s > -bits; s -= bits) v |= s >= 0 ? m << s : m >> -s;
+        return v & 255u;
+    }
+    if (bits == 0) return trits ? (digit == 2 ? 255u : 128u * digit) : (digit == 4 ? 255u : 64u * digit);  // (fewer than 6 levels: never a legal colour range)
+    static const unsigned ct[7] = {0, 204, 93, 44, 22, 11, 5}, cq[6] = {0, 113, 54, 26, 13, 6};
+    const unsigned a = m & 1u, x = m >> 1;  // x = the bits above a: b, cb, dcb, ...
+    unsigned B;
+    if (trits) B = bits == 1 ? 0 : bits == 2 ? 0x116u * x : bits == 3 ? (x << 7 | x << 2 | x) : bits == 4 ? (x << 6 | x) : bits == 5 ? (x << 5 | x >> 2) : (x << 4 | x >> 4);
+    else B = bits == 1 ? 0 : bits == 2 ? 0x10Cu * x : bits == 3 ? (x << 7 | x << 1 | x >> 1) : bits == 4 ? (x << 6 | x >> 1) : (x << 5 | x >> 3);
+    unsigned T = digit * (trits ? ct[bits] : cq[bits]) + B;
+    T ^= a ? 0x1FFu : 0u;
+    return ((a ? 0x80u : 0u) | (T >> 2)) & 255u;
+}
+static inline unsigned bu_astc_unq_weight(int bits, int trits, int quints, unsigned digit, unsigned m)
+{
+    unsigned w;
+    if (!trits && !quints) {
+        w = 0;
+        for (int s = 6 - bits; s > -bits; s -= bits) w |= s >= 0 ? m << s : m >> -s;
+        w &= 63u;
+    } else if (bits == 0) {
+        static const unsigned wt[3] = {0, 32, 63}, wq[5] = {0, 16, 32, 47, 63};
+        w = trits ? wt[digit] : wq[digit];
+    } else {
+        const unsigned a = m & 1u, x = m >> 1;
+        unsigned B, C;
+        if (trits) B = bits == 1 ? 0 : bits == 2 ? 0x45u * x : (x << 5 | x), C = bits == 1 ? 50 : bits == 2 ? 23 : 11;
+        else B = bits == 1 ? 0 : 0x42u * x, C = bits == 1 ? 28 : 13;
+        unsigned T = digit * C + B;
+        T ^= a ? 0x7Fu : 0u;
+        w = ((a ? 0x20u : 0u) | (T >> 2)) & 63u;
+    }
+    return w > 32 ? w + 1 : w;
+}
+
+static inline void bu_build_dec_tables(BuDecTables* d)
+{
+    for (int p = 0; p < 64; p++) {
+        uint32_t pat = 0;
+        for (int tx = 0; tx < 16; tx++) pat |= (uint32_t)((BU_BC7_PART2[p] >> tx) & 1u) << (2 * tx);
+        d->bc7_part[p].x = pat;
+        d->bc7_part[p].y = BU_BC7_ANCHORS[p];
+        d->bc7_part[64 + p].x = BU_BC7_PART3[p];
+        d->bc7_part[64 + p].y = BU_BC7_ANCHORS[64 + p];
+    }
+    for (int bits = 2; bits <= 4; bits++)
+        for (int i = 0; i < (1 << bits); i++) d->bc7_w[(1 << bits) - 4 + i] = (uint8_t)((64 * i + ((1 << bits) - 1) / 2) / ((1 << bits) - 1));
+    for (unsigned T = 0; T < 256; T++) {  // the specification's trit block
+        unsigned t[5], C;
+        if (((T >> 2) & 7u) == 7u) {
+            C = ((T >> 5) << 2) | (T & 3u);
+            t[4] = t[3] = 2;
+        } else {
+            C = T & 31u;
+            if (((T >> 5) & 3u) == 3u) t[4] = 2, t[3] = T >> 7;
+            else t[4] = T >> 7, t[3] = (T >> 5) & 3u;
+        }
+        if ((C & 3u) == 3u) {
+            t[2] = 2;
+            t[1] = C >> 4;
+            t[0] = ((C >> 2) & 2u) | (((C >> 2) & 1u) & ~(C >> 3));
+        } else if (((C >> 2) & 3u) == 3u) {
+            t[2] = t[1] = 2;
+            t[0] = C & 3u;
+        } else {
+            t[2] = C >> 4;
+            t[1] = (C >> 2) & 3u;
+            t[0] = (C & 2u) | ((C & 1u) & ~(C >> 1));
+        }
+        d->astc_trit[T] = (uint16_t)(t[0] | t[1] << 2 | t[2] << 4 | t[3] << 6 | t[4] << 8);
+    }
+    for (unsigned Q = 0; Q < 128; Q++) {  // the specification's quint block
+        unsigned q[3];
+        if (((Q >> 1) & 3u) == 3u && (Q >> 5) == 0u) {
+            q[2] = ((Q & 1u) << 2) | ((((Q >> 4) & ~Q) & 1u) << 1) | (((Q >> 3) & ~Q) & 1u);
+            q[1] = q[0] = 4;
+        } else {
+            unsigned C;
+            if (((Q >> 1) & 3u) == 3u) q[2] = 4, C = (((Q >> 3) & 3u) << 3) | ((~(Q >> 5) & 3u) << 1) | (Q & 1u);
+            else q[2] = Q >> 5, C = Q & 31u;
+            if ((C & 7u) == 5u) q[1] = 4, q[0] = C >> 3;
+            else q[1] = C >> 3, q[0] = C & 7u;
+        }
+        d->astc_quint[Q] = (uint16_t)(q[0] | q[1] << 3 | q[2] << 6);
+    }
+    unsigned cofs = 0, wofs = 0;
+    for (int r = 0; r < 21; r++) {
+        const int bits = BU_BISE[r].bits, tr = BU_BISE[r].trits, qu = BU_BISE[r].quints;
+        const unsigned digits = tr ? 3u : qu ? 5u : 1u;
+        d->astc_rng[r] = (uint8_t)(bits | tr << 4 | qu << 5);
+        d->astc_cofs[r] = (uint16_t)cofs;
+        if (r < 12) d->astc_wofs[r] = (uint8_t)wofs;
+        for (unsigned dg = 0; dg < digits; dg++)
+            for (unsigned m = 0; m < (1u << bits); m++) {
+                d->astc_cdeq[cofs + (dg << bits | m)] = (uint8_t)bu_astc_unq_colour(bits, tr, qu, dg, m);
+                if (r < 12) d->astc_wdeq[wofs + (dg << bits | m)] = (uint8_t)bu_astc_unq_weight(bits, tr, qu, dg, m);
+            }
+        cofs += digits << bits;
+        if (r < 12) wofs += digits << bits;
+    }
 }
 
 static inline void bu_build_tables(BuTablesAll* all)
@@ -470,4 +597,5 @@ static inline void bu_build_tables(BuTablesAll* all)
         t->eac_range[i] = (uint8_t)range;
         t->eac_magic[i] = (uint32_t)(((1u << 20) + 2 * range - 1) / (2 * range));  // exact for num*2*range < 2^20
     }
+    bu_build_dec_tables(&all->dec);
 }

@@ -377,6 +377,33 @@ bu_status bu_etc1s_transcode_rects_device(bu_context* ctx, bu_target target, siz
                                           const uint32_t* d_endpoints, uint32_t n_endpoints, const void* d_selectors, uint32_t n_selectors,
                                           uint64_t* d_status, void* stream);
 
+/* ---- block formats back to pixels --------------------------------------------
+ * The inverse direction: blocks of one of the ten block formats this library writes -> a row-major RGBA8 image, so that what was baked can be
+ * looked at, compared or sampled on the device that holds it.
+ *   format   BU_TARGET_ASTC (4x4 LDR), BC7, ETC1, ETC2 (RGBA: EAC alpha + ETC1 colour), BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB or BC3_RGBA;
+ *            any other value (RGBA32, the non-targets 5, 10, 13, negative values) is BU_ERR_ARGUMENT.
+ *   Block i = by * blocks_per_row + bx of the array covers pixels (4 bx .. 4 bx + 3, 4 by .. 4 by + 3); pixel (px, py) is written at
+ *   d_rgba + py * out_pitch_bytes + 4 * px, bytes R, G, B, A.  The decode rules, byte for byte, are DESIGN.md section 4.9: one-channel formats
+ *   give (v, 0, 0, 255), two-channel formats (x, y, 0, 255), BC3's colour half is always four-colour, EAC R11 scales its 11-bit value t to
+ *   (255 t + 1023) / 2047, ASTC decodes to UNORM8 (the top byte of the 16-bit result, no sRGB).
+ *   A block that cannot be decoded is written as 64 zero bytes and reported: BU_ERR_INVALID_MODE for a reserved or illegal encoding (BC7 with mode
+ *   byte 0, reserved / illegal ASTC), BU_ERR_UNSUPPORTED for a legal block outside the scope -- ETC2 T / H / planar colour blocks (in ETC1 and ETC2
+ *   alike), ASTC other than: a 4x4 weight grid, 1-4 partitions sharing one endpoint mode of 0, 4, 8 or 12, optional dual plane, LDR void extent.
+ *   The other eight formats have no invalid encodings.  d_status (optional) works as everywhere: min over failing blocks of
+ *   (block_index_base + i) << 8 | status; bu_status_word_decode decodes it.
+ * Device form: only enqueues on `stream` -- nothing is allocated, copied or synchronised, so it may be captured into a graph.  BU_ERR_ARGUMENT, with
+ * nothing launched, for: a format outside the ten; a null context; a null buffer with n_blocks > 0; blocks_per_row == 0 (or above 2^28);
+ * n_blocks % blocks_per_row != 0; d_blocks not aligned to the block size (8 or 16) or d_rgba not aligned to 16; an out_pitch_bytes that is
+ * neither 0 (= 16 * blocks_per_row) nor a multiple of 16 of at least 16 * blocks_per_row.  n_blocks == 0 is BU_OK and launches nothing.
+ * Host form: staging, one launch and the download as bu_uastc_decode_to_rgba (page-locked buffers of bu_host_alloc are read / written directly);
+ * tight pitch; BU_ERR_LENGTH when blocks_bytes is no multiple of the block size, BU_ERR_OUTPUT_SIZE when out_bytes < 64 * n, the block status
+ * and *first_bad_block as that call. */
+bu_status bu_blocks_decode_rgba_device(bu_context* ctx, bu_target format, const void* d_blocks, size_t n_blocks, void* d_rgba,
+                                       size_t blocks_per_row, size_t out_pitch_bytes, uint64_t block_index_base,
+                                       uint64_t* d_status, void* stream);
+bu_status bu_blocks_decode_rgba(bu_context* ctx, bu_target format, const uint8_t* blocks, size_t blocks_bytes,
+                                size_t blocks_per_row, uint8_t* out, size_t out_bytes, uint64_t* first_bad_block);
+
 /* ---- whole-file level: the crate's public read_to_* API (src/lib.rs:20-22, src/basis.rs) -------------
  * Host side in C++ (container parse, CRC-16, BasisLZ entropy decode -- byte/symbol serial, stays on the CPU),
  * block work on the GPU through the entry points above. */

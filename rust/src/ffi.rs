@@ -234,4 +234,10 @@ extern "C" {
     pub(crate) fn bu_etc1s_transcode_rects_device(ctx: *mut bu_context, target: c_int, n_jobs: usize, jobs: *const bu_etc1s_rect_job,
                                                   d_endpoints: *const u32, n_endpoints: u32, d_selectors: *const c_void, n_selectors: u32,
                                                   d_status: *mut u64, stream: *mut c_void) -> c_int;
+    // blocks of the ten block formats -> RGBA8 (tests/test_gpu_decode_blocks.py; `decode_blocks` / `decode_blocks_device` of lib.rs)
+    pub(crate) fn bu_blocks_decode_rgba_device(ctx: *mut bu_context, format: c_int, d_blocks: *const c_void, n_blocks: usize, d_rgba: *mut c_void,
+                                               blocks_per_row: usize, out_pitch_bytes: usize, block_index_base: u64, d_status: *mut u64,
+                                               stream: *mut c_void) -> c_int;
+    pub(crate) fn bu_blocks_decode_rgba(ctx: *mut bu_context, format: c_int, blocks: *const u8, blocks_bytes: usize, blocks_per_row: usize,
+                                        out: *mut u8, out_bytes: usize, first_bad_block: *mut u64) -> c_int;
 }

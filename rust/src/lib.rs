@@ -222,6 +222,38 @@ pub unsafe fn etc1s_transcode_rects_device(ctx: *mut ffi::bu_context, target: c_
     check(ctx, ffi::bu_etc1s_transcode_rects_device(ctx, target, jobs.len(), jobs.as_ptr(), d_endpoints, n_endpoints, d_selectors, n_selectors, d_status, stream))
 }
 
+/// Blocks of one of the ten block formats (`format`: `ffi::BU_TARGET_ASTC`, `BC7`, `ETC1`, `ETC2`, `BC4_R`, `BC5_RG`, `EAC_R11`, `EAC_RG11`,
+/// `BC1_RGB` or `BC3_RGBA`) in host memory -> the row-major RGBA8 image, `4 * blocks_per_row` pixels wide (bu_blocks_decode_rgba, no counterpart
+/// in the reference).  A block that cannot be decoded -- a reserved encoding, an ETC2 T / H / planar colour block, ASTC outside the 4x4 LDR
+/// scope -- is an `Err` naming the first such block.
+pub fn decode_blocks(format: c_int, blocks: &[u8], blocks_per_row: usize) -> Result<Vec<u8>> {
+    let ctx = context()?;
+    let bb = unsafe { ffi::bu_target_block_bytes(format) }.max(1);
+    let mut out = vec![0u8; (blocks.len() / bb * 64).max(1)];
+    let mut bad = 0u64;
+    let st = unsafe { ffi::bu_blocks_decode_rgba(ctx, format, blocks.as_ptr(), blocks.len(), blocks_per_row, out.as_mut_ptr(), out.len(), &mut bad) };
+    if st == 1 || st == 17 {
+        // BU_ERR_INVALID_MODE / BU_ERR_UNSUPPORTED of a block
+        return Err(format!("{} (block {})", status_string(st), bad));
+    }
+    check(ctx, st)?;
+    out.truncate(blocks.len() / bb * 64);
+    Ok(out)
+}
+
+/// The device form: `n_blocks` device-resident blocks of `format` -> an RGBA8 image at `d_rgba` with `out_pitch_bytes` per pixel row (0 = tight),
+/// in one enqueue on `stream` (bu_blocks_decode_rgba_device).  Only argument and launch errors are returned; a block that cannot be decoded is
+/// written as zeros and reported in `d_status`.
+///
+/// # Safety
+/// `ctx` is a live context; `d_blocks` holds `n_blocks` blocks, aligned to the block size; `d_rgba` (16-byte aligned) covers
+/// `4 * n_blocks / blocks_per_row` pixel rows of the pitch; `d_status` is null or a device status word; `stream` is null or a stream of that device.
+pub unsafe fn decode_blocks_device(ctx: *mut ffi::bu_context, format: c_int, d_blocks: *const core::ffi::c_void, n_blocks: usize,
+                                   d_rgba: *mut core::ffi::c_void, blocks_per_row: usize, out_pitch_bytes: usize, block_index_base: u64,
+                                   d_status: *mut u64, stream: *mut core::ffi::c_void) -> Result<()> {
+    check(ctx, ffi::bu_blocks_decode_rgba_device(ctx, format, d_blocks, n_blocks, d_rgba, blocks_per_row, out_pitch_bytes, block_index_base, d_status, stream))
+}
+
 /// Texture array sharded over the devices `devices` of one node (no counterpart in the reference, which walks the slices
 /// one by one: basis.rs:246-257): slice range g*n/P..(g+1)*n/P goes to device g, every device ends up holding the whole
 /// transcoded array (`gather = true`: peer pulls over xGMI), and the array is returned from device 0.

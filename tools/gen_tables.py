@@ -128,6 +128,25 @@ def bc1_solid_pairs(bits):
             for v in range(256)]
 
 
+# The partition shapes of the BPTC (BC7) specification, 4x4 texels in raster order.
+BC7_PART2 = [
+    0xCCCC, 0x8888, 0xEEEE, 0xECC8, 0xC880, 0xFEEC, 0xFEC8, 0xEC80, 0xC800, 0xFFEC, 0xFE80, 0xE800, 0xFFE8, 0xFF00, 0xFFF0, 0xF000,
+    0xF710, 0x008E, 0x7100, 0x08CE, 0x008C, 0x7310, 0x3100, 0x8CCE, 0x088C, 0x3110, 0x6666, 0x366C, 0x17E8, 0x0FF0, 0x718E, 0x399C,
+    0xAAAA, 0xF0F0, 0x5A5A, 0x33CC, 0x3C3C, 0x55AA, 0x9696, 0xA55A, 0x73CE, 0x13C8, 0x324C, 0x3BDC, 0x6996, 0xC33C, 0x9966, 0x0660,
+    0x0272, 0x04E4, 0x4E40, 0x2720, 0xC936, 0x936C, 0x39C6, 0x639C, 0x9336, 0x9CC6, 0x817E, 0xE718, 0xCCF0, 0x0FCC, 0x7744, 0xEE22,
+]
+BC7_PART3 = [
+    0xAA685050, 0x6A5A5040, 0x5A5A4200, 0x5450A0A8, 0xA5A50000, 0xA0A05050, 0x5555A0A0, 0x5A5A5050,
+    0xAA550000, 0xAA555500, 0xAAAA5500, 0x90909090, 0x94949494, 0xA4A4A4A4, 0xA9A59450, 0x2A0A4250,
+    0xA5945040, 0x0A425054, 0xA5A5A500, 0x55A0A0A0, 0xA8A85454, 0x6A6A4040, 0xA4A45000, 0x1A1A0500,
+    0x0050A4A4, 0xAAA59090, 0x14696914, 0x69691400, 0xA08585A0, 0xAA821414, 0x50A4A450, 0x6A5A0200,
+    0xA9A58000, 0x5090A0A8, 0xA8A09050, 0x24242424, 0x00AA5500, 0x24924924, 0x24499224, 0x50A50A50,
+    0x500AA550, 0xAAAA4444, 0x66660000, 0xA5A0A5A0, 0x50A050A0, 0x69286928, 0x44AAAA44, 0x66666600,
+    0xAA444444, 0x54A854A8, 0x95809580, 0x96969600, 0xA85454A8, 0x80959580, 0xAA141414, 0x96960000,
+    0xAAAA1414, 0xA05050A0, 0xA0A5A5A0, 0x96000000, 0x40804080, 0xA9A8A9A8, 0xAAAAAA44, 0x2A4A5254,
+]
+
+
 def fmt_array(ctype, name, vals, per_line=12, hexw=None):
     lines = []
     for i in range(0, len(vals), per_line):
@@ -319,6 +338,23 @@ def main():
     out.append(fmt_array("uint16_t", "BU_BC1_OM5", [a | (b << 8) for a, b in bc1_solid_pairs(5)], 12, 4))
     out.append("// the same for the 6-bit channel (e6)\n")
     out.append(fmt_array("uint16_t", "BU_BC1_OM6", [a | (b << 8) for a, b in bc1_solid_pairs(6)], 12, 4))
+
+    # ---- BPTC partition tables for the block decoder (bu_decode_blocks.hpp) ----
+    # All 64 + 64 partitions of the BPTC specification (the records above hold only the ones UASTC maps to).  The shapes are the
+    # specification's own tables, written here in their usual compact form: bit t of a 2-subset entry = subset of texel t, and 2 bits
+    # per texel, texel 0 low, for 3 subsets.  Self-check: every record above must agree with them.
+    assert len(BC7_PART2) == 64 and len(BC7_PART3) == 64
+    for r in recs[:30] + recs[60:]:
+        assert sum(((BC7_PART2[r[4]] >> t) & 1) << (2 * t) for t in range(16)) == r[3], r
+    for r in recs[30:60]:
+        assert BC7_PART3[r[4]] == r[3], r
+    out.append("// BPTC partitions, 2 subsets: bit t = subset of texel t (specification table \"partition table for 2 subset\")\n")
+    out.append(fmt_array("uint16_t", "BU_BC7_PART2", BC7_PART2, 12, 4))
+    out.append("// BPTC partitions, 3 subsets: 2 bits per texel, texel 0 low\n")
+    out.append(fmt_array("uint32_t", "BU_BC7_PART3", BC7_PART3, 8, 8))
+    out.append("// BPTC anchor texels: [p] = second subset's of 2-subset partition p; [64 + p] = a1 | a2 << 4 of 3-subset partition p (bc7.rs:701-722)\n")
+    assert all(a[0] == 0 for a in ba2) and all(a[0] == 0 for a in ba3)
+    out.append(fmt_array("uint8_t", "BU_BC7_ANCHORS", [a[1] for a in ba2] + [a[1] | (a[2] << 4) for a in ba3], 16, 2))
 
 
     # ======================= oracle tables (unpacked, formula-level) =======================
