@@ -311,6 +311,9 @@ BU_DEV int bu_dec_astc(const BuDecView& V, const uint32_t w[4], uint32_t px[16])
     if ((mode & 0x1FFu) == 0x1FCu) {  // void extent: a constant colour, UNORM16 -> the top byte
         if (mode & 0x200u) return BU_DEC_UNSUPPORTED;  // HDR
         if (((w[0] >> 10) & 3u) != 3u) return BU_DEC_INVALID;
+        // the extent, four 13-bit coordinates from bit 12: all ones = none; otherwise low < high on s and on t
+        const uint32_t s_lo = (w[0] >> 12) & 0x1FFFu, s_hi = (w[0] >> 25 | w[1] << 7) & 0x1FFFu, t_lo = (w[1] >> 6) & 0x1FFFu, t_hi = w[1] >> 19;
+        if ((s_lo & s_hi & t_lo & t_hi) != 0x1FFFu && (s_lo >= s_hi || t_lo >= t_hi)) return BU_DEC_INVALID;
         const uint32_t c = bu_dec_rgba((w[2] >> 8) & 255u, w[2] >> 24, (w[3] >> 8) & 255u, w[3] >> 24);
         BU_UNROLL
         for (int i = 0; i < 16; i++) px[i] = c;
@@ -318,7 +321,7 @@ BU_DEV int bu_dec_astc(const BuDecView& V, const uint32_t w[4], uint32_t px[16])
     }
     // block mode: only the layout with a 4-wide, 4-high weight grid is in scope (bits 2..3 = 0, A = 2, B = 0)
     if ((mode & 15u) == 0) return BU_DEC_INVALID;
-    if ((mode & 3u) == 0) return BU_DEC_UNSUPPORTED;
+    if ((mode & 3u) == 0) return ((mode >> 6) & 7u) == 7u ? BU_DEC_INVALID : BU_DEC_UNSUPPORTED;  // bits 6..8 all set: reserved (void extent left above)
     if (((mode >> 2) & 3u) != 0 || ((mode >> 5) & 3u) != 2u || ((mode >> 7) & 3u) != 0) return BU_DEC_UNSUPPORTED;
     const uint32_t R = ((mode >> 4) & 1u) | (mode & 3u) << 1, hp = (mode >> 9) & 1u, dual = (mode >> 10) & 1u;
     if (R < 2u) return BU_DEC_INVALID;

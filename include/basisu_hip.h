@@ -389,6 +389,9 @@ bu_status bu_etc1s_transcode_rects_device(bu_context* ctx, bu_target target, siz
  *   A block that cannot be decoded is written as 64 zero bytes and reported: BU_ERR_INVALID_MODE for a reserved or illegal encoding (BC7 with mode
  *   byte 0, reserved / illegal ASTC), BU_ERR_UNSUPPORTED for a legal block outside the scope -- ETC2 T / H / planar colour blocks (in ETC1 and ETC2
  *   alike), ASTC other than: a 4x4 weight grid, 1-4 partitions sharing one endpoint mode of 0, 4, 8 or 12, optional dual plane, LDR void extent.
+ *   Reserved / illegal ASTC includes the block modes the specification's table reserves (bits 0-3 = 0000; bits 0-1 = 00 with bits 6-8 = 111 other
+ *   than void extent) and a void-extent block whose extent is neither all ones nor ordered (low < high on s and on t).  Stated deviations: a
+ *   weight grid larger than the 4x4 footprint, and HDR content, are BU_ERR_UNSUPPORTED although the LDR 4x4 profile makes them illegal.
  *   The other eight formats have no invalid encodings.  d_status (optional) works as everywhere: min over failing blocks of
  *   (block_index_base + i) << 8 | status; bu_status_word_decode decodes it.
  * Device form: only enqueues on `stream` -- nothing is allocated, copied or synchronised, so it may be captured into a graph.  BU_ERR_ARGUMENT, with

@@ -293,7 +293,10 @@ int bu_dec_astc_4x4(const uint8_t b[16], uint8_t out[64])
     if ((mode & 0x1FF) == 0x1FC) { /* void extent */
         if (mode & 0x200) return DEC_UNSUPPORTED; /* HDR */
         if (get_bits(b, 10, 2) != 3) return DEC_RESERVED;
-        /* extent coordinates: all ones = no extent; otherwise they must be ordered -- either way the colour is constant */
+        /* extent coordinates: all ones = no extent; otherwise low < high on s and on t -- then the colour is constant either way */
+        const unsigned s_lo = get_bits(b, 12, 13), s_hi = get_bits(b, 25, 13), t_lo = get_bits(b, 38, 13), t_hi = get_bits(b, 51, 13);
+        const int no_extent = s_lo == 0x1FFF && s_hi == 0x1FFF && t_lo == 0x1FFF && t_hi == 0x1FFF;
+        if (!no_extent && (s_lo >= s_hi || t_lo >= t_hi)) return DEC_ILLEGAL;
         for (int t = 0; t < 16; t++)
             for (int c = 0; c < 4; c++) out[4 * t + c] = (uint8_t)(get_bits(b, 64 + 16 * c, 16) >> 8);
         return DEC_OK;
@@ -315,6 +318,7 @@ int bu_dec_astc_4x4(const uint8_t b[16], uint8_t out[64])
             break;
         }
     } else {
+        if (((mode >> 6) & 7) == 7) return DEC_RESERVED; /* bits 6..8 all set and not void-extent: reserved by the block-mode table */
         return DEC_UNSUPPORTED; /* the large-grid layouts cannot describe 4x4 */
     }
     if (W != 4 || H != 4) return DEC_UNSUPPORTED;

@@ -7,7 +7,12 @@ expected(dec, fmt, blocks)   -> (texels [n, 64] uint8, status [n]) from
     tests/channel_model.py: bc4_decode / r11_decode   BC4, BC5, BC3's alpha half, EAC R11 / RG11
   with the rounding of section 4.9: an exact rational num / den becomes (2 num + den) // (2 den); R11's 11-bit t becomes (255 t + 1023) // 2047.
   A failing block is 64 zero bytes with status 1 (BU_ERR_INVALID_MODE: the oracle's RESERVED and ILLEGAL) or 17 (BU_ERR_UNSUPPORTED).
+emul_decoder(tmp_path_factory) -> the product's block code as a stand-alone ASan + UBSan program, for tests/test_decode_blocks.py and
+  tests/test_decode_fields.py (the latter judges ASTC and BC7 -- and oracle/bu_decoders.c itself -- by tests/astc_model.py and a third party).
 """
+import os
+import subprocess
+
 import numpy as np
 
 import channel_model as cm
@@ -19,6 +24,37 @@ FORMATS = {"astc": _lib.ASTC, "bc7": _lib.BC7, "etc1": _lib.ETC1, "etc2": _lib.E
 BLOCK_BYTES = {k: _lib.BLOCK_BYTES[v] for k, v in FORMATS.items()}
 OK, INVALID, UNSUPPORTED = 0, _lib.ERR_INVALID_MODE, _lib.ERR_UNSUPPORTED
 ORACLE_CLASS = np.array([OK, INVALID, UNSUPPORTED, INVALID])  # DEC_OK, DEC_RESERVED, DEC_UNSUPPORTED, DEC_ILLEGAL of bu_decoders.c
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_EMUL = []
+
+
+def emul_decoder(tmp_path_factory):
+    """fmt, blocks -> (texels [n, 64], status [n]) through the sanitizer build of the product's block code (tests/host_emul/bu_emul_decode_main.cpp
+    under AddressSanitizer and UBSan), a child process per call; compiled once per session"""
+    if _EMUL:
+        return _EMUL[0]
+    d = tmp_path_factory.mktemp("emul_decode")
+    exe = str(d / "bu_emul_decode")
+    src = os.path.join(ROOT, "tests", "host_emul", "bu_emul_decode_main.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wno-unknown-pragmas",
+                        "-I" + os.path.join(ROOT, "basisu_rs_amd", "csrc"), "-o", exe, src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+    def run(fmt, blocks):
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1, BLOCK_BYTES[fmt])
+        n = blocks.shape[0]
+        with open(d / "in.bin", "wb") as f:
+            f.write(np.int32(FORMATS[fmt]).tobytes() + blocks.tobytes())
+        r = subprocess.run([exe, str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
+        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+        o = np.fromfile(d / "out.bin", dtype=np.uint8)
+        assert o.size == 65 * n
+        return o[: 64 * n].reshape(n, 64), o[64 * n:].astype(np.int64)
+
+    _EMUL.append(run)
+    return run
 
 
 def _round(num, den):
@@ -172,13 +208,16 @@ def edge_blocks():
     reps = -(-e["etc1"].shape[0] // alpha.shape[0])
     e["etc2"] = np.concatenate([np.tile(alpha, (reps, 1))[: e["etc1"].shape[0]], e["etc1"]], axis=1)
     # ASTC: LDR void-extent blocks (all-ones extent), an HDR one (unsupported) and one with the reserved bits clear (invalid)
-    def void(bits12, rgba16):
-        w = 0x1FC | (bits12 << 9) | (((1 << 52) - 1) << 12)
+    # then an extent that is ordered (s 10..20, t 5..30: decodes), one that is not (s 20..10: invalid) and a reserved block mode (bits 0-1 = 00,
+    # bits 6-8 = 111, not void-extent: invalid)
+    def void(bits12, rgba16, extent=(0x1FFF, 0x1FFF, 0x1FFF, 0x1FFF)):
+        w = 0x1FC | (bits12 << 9) | sum(v << (12 + 13 * k) for k, v in enumerate(extent))
         b = list(int(w).to_bytes(8, "little"))
         for v in rgba16:
             b += [v & 255, v >> 8]
         return b
     e["astc"] = np.array([void(6, (0x1234, 0xFFFF, 0x0000, 0x80FF)), void(6, (0xFF00, 0x00FF, 0x7F80, 0xFFFF)), void(7, (0x3C00, 0x3C00, 0x3C00, 0x3C00)),
-                          void(2, (1, 2, 3, 4)), void(0, (1, 2, 3, 4))], dtype=np.uint8)
+                          void(2, (1, 2, 3, 4)), void(0, (1, 2, 3, 4)), void(6, (0x1234, 0xFFFF, 0x0000, 0x80FF), (10, 20, 5, 30)),
+                          void(6, (0x1234, 0xFFFF, 0x0000, 0x80FF), (20, 10, 5, 30)), [0xC4, 0x01] + [0x55] * 14], dtype=np.uint8)
     e["bc7"] = np.array([[0] * 16, [0] + [0xFF] * 15, [0x80] + [0] * 15, [0x80] + [0xFF] * 15, [0x40] + [0xFF] * 15, [0x01] + [0xFF] * 15], dtype=np.uint8)
     return e
