@@ -123,6 +123,19 @@ static unsigned bu_etc1s_file_slot(const BuFilePlan& p, bu_read_target target)
     return p.etc1s_six ? bu_etc1s_target_slot(bu_read_block_target(target)) : target == BU_READ_RGBA ? 1u : 0u;
 }
 
+// BU_TRACE: the time since the previous lap, one line per step of a call
+struct BuLap {
+    const bool on;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char* what)
+    {
+        if (!on) return;
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[bu_read_to] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
+        t_prev = t;
+    }
+};
+
 // ---- streamed ETC1S front door -------------------------------------------------------------------------------------------------
 // A slice's symbol stream is serial (one host core: 1.86 ms of BASELINE config 4's 2.6), and everything else used to queue up in
 // front of and behind it: payload CRC 0.12 ms, codebooks 0.19 ms, upload + kernel + download 0.4 ms.  Here they run BESIDE it:
@@ -136,69 +149,32 @@ static unsigned bu_etc1s_file_slot(const BuFilePlan& p, bu_read_target target)
 constexpr size_t BU_ETC1S_STREAM_MIN_BLOCKS = 32768, BU_ETC1S_BAND_BLOCKS = 16384;
 
 static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, const BuFilePlan& p, uint8_t* out,
-                                        bool crc_pending, uint16_t crc_want, bool trace)
+                                        bool crc_pending, uint16_t crc_want, BuLap& lap)
 {
     using bu_host::in_file;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_prev = now();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        const auto t = now();
-        fprintf(stderr, "[bu_read_to] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-        t_prev = t;
-    };
+    const bool trace = lap.on;
     const bu_basis_header& h = p.h;
+    // (the pool is not taken yet: the pooled CRC)
+    const auto leave = [&](bu_status s) { return (crc_pending && bu_host::crc16(file + 77, len - 77, 0) != crc_want) ? BU_ERR_DATA_CRC : s; };
     if (!in_file(len, h.endpoint_cb_file_ofs, h.endpoint_cb_file_size) || !in_file(len, h.selector_cb_file_ofs, h.selector_cb_file_size) ||
         !in_file(len, h.tables_file_ofs, h.tables_file_size) || !in_file(len, h.extended_file_ofs, h.extended_file_size))
-        return (crc_pending && bu_host::crc16(file + 77, len - 77, 0) != crc_want) ? BU_ERR_DATA_CRC : BU_ERR_BOUNDS;  // (pool not taken yet)
+        return leave(BU_ERR_BOUNDS);
     bu_host::BasisLz lz;
     // total_selectors for both codebooks: basis.rs:289-291
     const bu_status st_tables = lz.init_tables(h.total_selectors, h.total_selectors, file + h.tables_file_ofs, h.tables_file_size, h.tex_type == 3);
     lap("tables");
     const size_t n_img = p.images.size();
-    auto align_up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // layout of the index buffer and the kernel's slice table, as in the one-launch path
-    std::vector<size_t> in_off(n_img, 0), ain_off(n_img, 0);
-    size_t words = 0;
-    for (size_t k = 0; k < n_img; k++) {
-        const bu_slice_desc& s = p.slices[p.first_slice[k]];
-        const size_t nblk = (size_t)s.num_blocks_x * s.num_blocks_y;
-        in_off[k] = words;
-        words += (nblk + 63) & ~(size_t)63;
-        if (p.alpha_pairs) {
-            ain_off[k] = words;
-            words += (nblk + 63) & ~(size_t)63;
-        }
-    }
-    std::vector<BuEtc1sSlice> descs;
-    std::vector<uint32_t> unit0(n_img, 0), units_of(n_img, 0);
-    uint32_t n_units = 0;
-    for (size_t k = 0; k < n_img; k++) {
-        const bu_slice_desc& sl = p.slices[p.first_slice[k]];
-        const size_t nblk = (size_t)sl.num_blocks_x * sl.num_blocks_y;
-        unit0[k] = n_units;
-        if (p.images[k].size == 0 || nblk == 0) continue;
-        BuEtc1sSlice d;
-        d.unit0 = n_units;
-        d.n_blocks = (uint32_t)nblk;
-        d.nbx = sl.num_blocks_x;
-        d.idx_ofs = (uint32_t)in_off[k];
-        d.aidx_ofs = p.alpha_pairs ? (uint32_t)ain_off[k] : 0xFFFFFFFFu;
-        d.image = (uint32_t)k;
-        d.out_ofs = p.images[k].offset;
-        descs.push_back(d);
-        units_of[k] = (uint32_t)((nblk + 63) / 64);
-        n_units += units_of[k];
-    }
-    BuEtc1sSlice end = {};
-    end.unit0 = n_units;
-    descs.push_back(end);
+    BuEtc1sFileLayout l;
+    bu_status st = bu_etc1s_file_layout(p, l);
+    if (st) return leave(st);
+    const std::vector<BuEtc1sSlice>& descs = l.descs;
+    const std::vector<uint32_t>&unit0 = l.unit0, &units_of = l.units_of;
 
     std::lock_guard<std::mutex> g(ctx->lock);
     BU_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> status_words(n_img, 0);  // landing area of the status download: outlives the drain
     BuDrain drain(ctx);
-    const size_t idx_bytes = (words ? words : 16) * 4;
+    const size_t idx_bytes = (l.words ? l.words : 16) * 4;
     if (idx_bytes > ctx->h_idx_cap) {
         if (ctx->h_idx) BU_HIP(ctx, hipHostFree(ctx->h_idx));
         ctx->h_idx = nullptr;
@@ -212,11 +188,10 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     if (!bu_device_view(h_idx, &d_idx_view)) return BU_ERR_HIP;
     void* zout = nullptr;
     const bool direct_out = bu_device_view(out, &zout);
-    bu_status st;
     if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
     const size_t n_cb = h.total_selectors;
-    const size_t ep_bytes = align_up(n_cb * 4), sel_bytes = align_up(n_cb * 8), status_bytes = align_up(8 * n_img),
-                 desc_bytes = align_up(descs.size() * sizeof(BuEtc1sSlice));
+    const size_t ep_bytes = bu_align256(n_cb * 4), sel_bytes = bu_align256(n_cb * 8), status_bytes = bu_align256(8 * n_img),
+                 desc_bytes = bu_align256(descs.size() * sizeof(BuEtc1sSlice));
     if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + 256))) return st;
     uint8_t* const aux = static_cast<uint8_t*>(ctx->d_aux);
     uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
@@ -262,7 +237,7 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
             j.nby = s.num_blocks_y;
             j.data = file + s.file_ofs;
             j.len = s.file_size;
-            j.idx = h_idx + (a ? ain_off[k] : in_off[k]);
+            j.idx = h_idx + (a ? l.aidx_ofs[k] : l.idx_ofs[k]);
             if (may_split && j.nbx * j.nby >= BU_ETC1S_STREAM_MIN_BLOCKS) {
                 j.split = true;
                 tok_bytes += (j.nbx * j.nby * 6 + 127) & ~(size_t)63;
@@ -523,187 +498,114 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     return BU_OK;
 }
 
-// etc1s_six: the call is bu_read_file_to (bu_plan_file)
-static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, bu_basis_header* header_out, bu_image* images,
-                                size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes, bool etc1s_six = false)
+// ---- UASTC file to BU_READ_UASTC: plain copies, no device work (uastc.rs:85-87) ---------------------------------------------------
+static bu_status bu_read_uastc_copy(const uint8_t* file, const BuFilePlan& p, uint8_t* out)
 {
-    if (!ctx || !out) return BU_ERR_ARGUMENT;
-    const bool trace = getenv("BU_TRACE") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_prev = now();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        const auto t = now();
-        fprintf(stderr, "[bu_read_to] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-        t_prev = t;
-    };
-    BuFilePlan p;
-    // Large UASTC files: the payload CRC (0.7 ms per 16 MiB on the host cores -- as long as upload, kernel and download
-    // together) is computed ON THE DEVICE over the slice bytes the call uploads anyway (bu_crc16_pieces_kernel, one
-    // register per 64 KiB piece); the host only runs the bytes the device never sees (slice table, gaps, the tail of a run
-    // behind its last whole piece) and folds everything in file order.  The reference checks the CRC before anything else
-    // behind the header (basis.rs:338-341), so a CRC failure takes precedence over every later error, and nothing is
-    // reported as success before it is known; an early error return settles it on the host.
-    bool crc_deferred = false;
-    uint16_t crc_want = 0;
-    {
-        bu_basis_header h0;
-        if (file && len >= ((size_t)1 << 20) && bu_host::read_header(file, len, &h0) == BU_OK && h0.tex_format == 1 && target != BU_READ_UASTC) {
-            crc_deferred = true;
-            crc_want = h0.data_crc16;
-        }
-        // ETC1S files of some size: the payload CRC runs on a pool thread beside the entropy decode (bu_read_etc1s_streamed)
-        if (file && len >= ((size_t)64 << 10) && !getenv("BU_ETC1S_ONE_LAUNCH") && bu_host::read_header(file, len, &h0) == BU_OK && h0.tex_format == 0) {
-            crc_deferred = true;
-            crc_want = h0.data_crc16;
-        }
+    for (size_t k = 0; k < p.images.size(); k++) {
+        const bu_slice_desc& s = p.slices[p.first_slice[k]];
+        if (s.file_size) memcpy(out + p.images[k].offset, file + s.file_ofs, s.file_size);
     }
-    auto settle = [&](bu_status s) {  // the status to report once the deferred CRC is known
-        if (crc_deferred) {
-            crc_deferred = false;
-            if (bu_host::crc16(file + 77, len - 77, 0) != crc_want) return BU_ERR_DATA_CRC;
-        }
-        return s;
-    };
-    bu_status st = bu_plan_file(target, file, len, p, !crc_deferred, etc1s_six);
-    lap("plan (parse + CRCs)");
-    if (st) return settle(st);
-    const auto rest = [&]() -> bu_status {
-    if (header_out) *header_out = p.h;
-    if (n_images) *n_images = p.images.size();
-    if (out_bytes < p.out_bytes) return BU_ERR_OUTPUT_SIZE;
-    if (images) {
-        if (p.images.size() > max_images) return BU_ERR_OUTPUT_SIZE;
-        for (size_t i = 0; i < p.images.size(); i++) images[i] = p.images[i];
-    }
-    if (p.images.empty()) return BU_OK;
-    if (!p.etc1s && target == BU_READ_UASTC) {  // uastc.rs:85-87: plain copies, no device work
-        for (size_t k = 0; k < p.images.size(); k++) {
-            const bu_slice_desc& s = p.slices[p.first_slice[k]];
-            if (s.file_size) memcpy(out + p.images[k].offset, file + s.file_ofs, s.file_size);
-        }
-        return BU_OK;
-    }
-    // Batched front door: every slice's input is staged at an aligned offset of one device buffer, the device output
-    // buffer mirrors `out`, all launches go to the context stream back to back (one status word per image) and a
-    // single synchronisation ends the call.  The host-side BasisLZ decode of all slices happens before any upload.
-    if (p.etc1s && !getenv("BU_ETC1S_ONE_LAUNCH")) {
-        size_t total_blocks = 0;
-        for (size_t k = 0; k < p.images.size(); k++) total_blocks += (size_t)p.slices[p.first_slice[k]].num_blocks_x * p.slices[p.first_slice[k]].num_blocks_y;
-        if (total_blocks >= BU_ETC1S_STREAM_MIN_BLOCKS) {
-            const bool pending = crc_deferred;
-            crc_deferred = false;  // settled inside (on a pool thread); nothing is left for settle()
-            return bu_read_etc1s_streamed(ctx, target, file, len, p, out, pending, crc_want, trace);
-        }
-    }
-    bu_host::BasisLz lz;
+    return BU_OK;
+}
+
+// ---- ETC1S file in one launch (files below BU_ETC1S_STREAM_MIN_BLOCKS, BU_ETC1S_ONE_LAUNCH) ---------------------------------------
+// The symbol streams of all slices are decoded on the host cores before anything is uploaded; index buffer, codebooks and slice table go up
+// on the context stream, ONE launch serves the whole file (basis.rs:42-58 / 103-123 walk the slices one by one; one status word per image),
+// and a single synchronisation ends the call.  The device output buffer mirrors `out`.
+static bu_status bu_read_etc1s_one_launch(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, const BuFilePlan& p, uint8_t* out, BuLap& lap)
+{
     const size_t n_img = p.images.size();
-    std::vector<size_t> in_off(n_img, 0), ain_off(n_img, 0), run_of(n_img, 0);  // run_of[k]: first image of k's run
-    std::vector<uint32_t> idx_all;
-    size_t total_in = 0;
-    auto align_up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    if (p.etc1s) {
-        st = bu_make_lz(file, len, p.h, lz);
-        if (st) return st;
-        lap("codebooks + tables");
-        size_t words = 0;
-        for (size_t k = 0; k < n_img; k++) {
-            const bu_slice_desc& s = p.slices[p.first_slice[k]];
-            const size_t nblk = (size_t)s.num_blocks_x * s.num_blocks_y;
-            in_off[k] = words * 4;
-            words += (nblk + 63) & ~(size_t)63;
-            if (p.alpha_pairs) {
-                ain_off[k] = words * 4;
-                words += (nblk + 63) & ~(size_t)63;
-            }
+    bu_host::BasisLz lz;
+    bu_status st = bu_make_lz(file, len, p.h, lz);
+    if (st) return st;
+    lap("codebooks + tables");
+    BuEtc1sFileLayout l;
+    if ((st = bu_etc1s_file_layout(p, l))) return st;
+    std::vector<uint32_t> idx_all(l.words ? l.words : 1, 0);
+    std::vector<bu_host::SliceJob> jobs;  // file order: colour slice, then its alpha slice
+    jobs.reserve(n_img * (p.alpha_pairs ? 2 : 1));
+    for (size_t k = 0; k < n_img; k++)
+        for (size_t a = 0; a < (p.alpha_pairs ? 2u : 1u); a++) {
+            const bu_slice_desc& s = p.slices[p.first_slice[k] + a];
+            jobs.push_back({s.num_blocks_x, s.num_blocks_y, file + s.file_ofs, s.file_size, idx_all.data() + (a ? l.aidx_ofs[k] : l.idx_ofs[k]), BU_OK});
         }
-        idx_all.assign(words ? words : 1, 0);
-        std::vector<bu_host::SliceJob> jobs;  // file order: colour slice, then its alpha slice
-        jobs.reserve(n_img * (p.alpha_pairs ? 2 : 1));
-        for (size_t k = 0; k < n_img; k++) {
-            const bu_slice_desc& s = p.slices[p.first_slice[k]];
-            jobs.push_back({s.num_blocks_x, s.num_blocks_y, file + s.file_ofs, s.file_size, idx_all.data() + in_off[k] / 4, BU_OK});
-            if (p.alpha_pairs) {
-                const bu_slice_desc& a = p.slices[p.first_slice[k] + 1];
-                jobs.push_back({a.num_blocks_x, a.num_blocks_y, file + a.file_ofs, a.file_size, idx_all.data() + ain_off[k] / 4, BU_OK});
-            }
-        }
-        st = bu_host::decode_slices(lz, jobs);  // host cores in parallel; the symbol stream is serial only within a slice
-        if (st) return st;
-        lap("slice symbol streams");
-        total_in = words * 4;
-    } else {
-        // Runs: consecutive slices that sit back to back in the file (the usual layout of a mip chain or a texture array)
-        // are staged back to back with ONE upload, and -- for the block-linear targets, whose outputs are then contiguous
-        // too -- transcoded with ONE launch over the whole run: 512 slices of 65 536 blocks are one 33 M-block launch
-        // (0.3 ms) instead of 512 latency-bound ones (3.9 ms).  The lowest failing block of a run lies in its first
-        // failing slice, so the reported error is the sequential loop's.
-        for (size_t k = 0; k < n_img; k++) {
-            const bu_slice_desc& s = p.slices[p.first_slice[k]];
-            const bool joins = k > 0 && run_of[k - 1] != SIZE_MAX && s.file_size % 16 == 0 && s.file_size != 0 &&
-                               p.slices[p.first_slice[k - 1]].file_size % 16 == 0 && p.slices[p.first_slice[k - 1]].file_size != 0 &&
-                               (size_t)p.slices[p.first_slice[k - 1]].file_ofs + p.slices[p.first_slice[k - 1]].file_size == s.file_ofs;
-            if (joins) {
-                run_of[k] = run_of[k - 1];
-                in_off[k] = in_off[k - 1] + p.slices[p.first_slice[k - 1]].file_size;
-                total_in = in_off[k] + s.file_size;
-            } else {
-                total_in = align_up(total_in);
-                run_of[k] = k;
-                in_off[k] = total_in;
-                total_in += s.file_size;
-            }
-        }
-        total_in = align_up(total_in);
-    }
+    st = bu_host::decode_slices(lz, jobs);  // host cores in parallel; the symbol stream is serial only within a slice
+    if (st) return st;
+    lap("slice symbol streams");
+    const size_t total_in = l.words * 4;
     std::lock_guard<std::mutex> g(ctx->lock);
     BU_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> words(n_img, 0);  // status landing area: declared before anything is queued, outlives the drain
-    std::vector<BuEtc1sSlice> descs;        // (likewise: source of an upload)
-    struct CrcSeg {
-        size_t file_ofs, len, first_piece, n_pieces;
-    };
-    std::vector<CrcSeg> crc_segs;           // uploaded file ranges whose 64 KiB pieces the device registers
-    std::vector<uint16_t> crc_parts((crc_deferred && !p.etc1s) ? total_in / BU_CRC_PIECE + 1 : 1, 0);  // (landing area too)
-    size_t crc_pieces = 0;
     BuDrain drain(ctx);
     if ((st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, total_in ? total_in : 16))) return st;
     // a page-locked `out` (bu_host_alloc) receives the kernels' stores directly over PCIe: no device output buffer, no download
     void* zout = nullptr;
     const bool direct_out = bu_device_view(out, &zout);
     if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
-    const size_t ep_bytes = p.etc1s ? align_up(lz.endpoints.size() * 4) : 0, sel_bytes = p.etc1s ? align_up(lz.selectors.size()) : 0;
-    // ETC1S: one descriptor per image (+ sentinel) behind the codebooks and the status words
-    uint32_t n_units = 0;
-    if (p.etc1s) {
-        descs.reserve(n_img + 1);
-        for (size_t k = 0; k < n_img; k++) {
-            const bu_slice_desc& sl = p.slices[p.first_slice[k]];
-            const size_t nblk = (size_t)sl.num_blocks_x * sl.num_blocks_y;
-            if (p.images[k].size == 0 || nblk == 0) continue;
-            BuEtc1sSlice d;
-            d.unit0 = n_units;
-            d.n_blocks = (uint32_t)nblk;
-            d.nbx = sl.num_blocks_x;
-            d.idx_ofs = (uint32_t)(in_off[k] / 4);
-            d.aidx_ofs = p.alpha_pairs ? (uint32_t)(ain_off[k] / 4) : 0xFFFFFFFFu;
-            d.image = (uint32_t)k;
-            d.out_ofs = p.images[k].offset;
-            descs.push_back(d);
-            n_units += (uint32_t)((nblk + 63) / 64);
-        }
-        BuEtc1sSlice end = {};
-        end.unit0 = n_units;
-        descs.push_back(end);
+    // behind the codebooks: the status words, then one descriptor per image (+ sentinel)
+    const size_t ep_bytes = bu_align256(lz.endpoints.size() * 4), sel_bytes = bu_align256(lz.selectors.size()), status_bytes = bu_align256(8 * n_img),
+                 desc_bytes = bu_align256(l.descs.size() * sizeof(BuEtc1sSlice));
+    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + 512))) return st;
+    uint8_t* const d_in = static_cast<uint8_t*>(ctx->d_in);
+    uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
+    uint8_t* const aux = static_cast<uint8_t*>(ctx->d_aux);
+    uint64_t* const d_status = reinterpret_cast<uint64_t*>(aux + ep_bytes + sel_bytes);
+    BuEtc1sSlice* const d_descs = reinterpret_cast<BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
+    BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
+    BU_HIP(ctx, hipMemcpyAsync(d_in, idx_all.data(), total_in, hipMemcpyHostToDevice, ctx->stream));
+    if (!lz.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, lz.endpoints.data(), lz.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!lz.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, lz.selectors.data(), lz.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
+    BU_HIP(ctx, hipMemcpyAsync(d_descs, l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
+    if (l.n_units) {
+        const unsigned grid = bu_grid_for((size_t)l.n_units * 64, ctx->cu_count);
+        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(l.descs.size() - 1), 0u, l.n_units,
+                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), (uint32_t)lz.endpoints.size(), d_out, d_status);
+        BU_HIP(ctx, hipGetLastError());
     }
-    const size_t desc_bytes = align_up(descs.size() * sizeof(BuEtc1sSlice)), status_bytes = align_up(8 * n_img);
-    const size_t crc_bytes = align_up(2 * crc_parts.size());
-    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + crc_bytes + 256))) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->d_in);
-    uint8_t* d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
-    uint8_t* aux = static_cast<uint8_t*>(ctx->d_aux);
-    uint64_t* d_status = reinterpret_cast<uint64_t*>(aux + ep_bytes + sel_bytes);
-    uint16_t* d_crc = reinterpret_cast<uint16_t*>(aux + ep_bytes + sel_bytes + status_bytes + desc_bytes);
+    lap("reserve + enqueue");
+    BU_HIP(ctx, hipGetLastError());
+    BU_HIP(ctx, hipMemcpyAsync(words.data(), d_status, 8 * n_img, hipMemcpyDeviceToHost, ctx->stream));
+    if (p.out_bytes && !direct_out) BU_HIP(ctx, hipMemcpyAsync(out, d_out, p.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drain.armed = false;
+    lap("download + synchronise");
+    for (size_t k = 0; k < n_img; k++)  // first Err (in slice order) aborts the whole call, like the `?` in the reference drivers
+        if ((st = bu_status_word_decode(words[k], nullptr))) return st;
+    return BU_OK;
+}
+
+// ---- UASTC file through the kernels -------------------------------------------------------------------------------------------------
+// Every run of slices (bu_file_layout.hpp) is staged at an aligned offset of one device buffer with one upload, the device output buffer
+// mirrors `out`, all launches go to the context stream back to back (one status word per image) -- large runs with a mapped output in
+// pieces on two streams -- and a single synchronisation ends the call.
+// crc_deferred: the payload CRC (0.7 ms per 16 MiB on the host cores -- as long as upload, kernel and download together) is computed ON THE
+// DEVICE over the slice bytes the call uploads anyway (bu_crc16_pieces_kernel, one register per 64 KiB piece) and folded at the end
+// (bu_crc_fold), which clears the flag; an earlier error return leaves it set.
+static bu_status bu_read_uastc_runs(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, const BuFilePlan& p, uint8_t* out, bool& crc_deferred,
+                                    uint16_t crc_want, BuLap& lap)
+{
+    const size_t n_img = p.images.size();
+    BuUastcFileLayout l;
+    bu_uastc_file_layout(p, l);
+    std::lock_guard<std::mutex> g(ctx->lock);
+    BU_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> words(n_img, 0);  // status landing area: declared before anything is queued, outlives the drain
+    std::vector<BuCrcSeg> crc_segs;         // uploaded file ranges whose 64 KiB pieces the device registers
+    std::vector<uint16_t> crc_parts(crc_deferred ? l.total_in / BU_CRC_PIECE + 1 : 1, 0);  // (landing area too)
+    size_t crc_pieces = 0;
+    BuDrain drain(ctx);
+    bu_status st;
+    if ((st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, l.total_in ? l.total_in : 16))) return st;
+    // a page-locked `out` (bu_host_alloc) receives the kernels' stores directly over PCIe: no device output buffer, no download
+    void* zout = nullptr;
+    const bool direct_out = bu_device_view(out, &zout);
+    if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
+    const size_t status_bytes = bu_align256(8 * n_img), crc_bytes = bu_align256(2 * crc_parts.size());
+    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, status_bytes + crc_bytes + 256))) return st;
+    uint8_t* const d_in = static_cast<uint8_t*>(ctx->d_in);
+    uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
+    uint64_t* const d_status = static_cast<uint64_t*>(ctx->d_aux);
+    uint16_t* const d_crc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(ctx->d_aux) + status_bytes);
     // registers of the whole 64 KiB pieces of an uploaded range, on the stream that carries its upload
     auto crc_enqueue = [&](const uint8_t* d_range, size_t file_ofs, size_t nbytes, hipStream_t ps) {
         if (!crc_deferred) return;
@@ -713,94 +615,48 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
         crc_pieces += np;
     };
     BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
-    if (p.etc1s) {
-        BU_HIP(ctx, hipMemcpyAsync(d_in, idx_all.data(), total_in, hipMemcpyHostToDevice, ctx->stream));
-        if (!lz.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, lz.endpoints.data(), lz.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (!lz.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, lz.selectors.data(), lz.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
-        BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes + sel_bytes + status_bytes, descs.data(), descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
-        // ONE launch for the whole file (basis.rs:42-58 / 103-123 walk the slices one by one)
-        if (n_units) {
-            const uint32_t n_cb0 = (uint32_t)lz.endpoints.size();
-            const unsigned grid = bu_grid_for((size_t)n_units * 64, ctx->cu_count);
-            const BuEtc1sSlice* d_descs = reinterpret_cast<const BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
-            bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(descs.size() - 1), 0u, n_units,
-                                 reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
-            BU_HIP(ctx, hipGetLastError());
-        }
-    }
     int used_extra = 0;  // own streams 0..used_extra-1 carry pieces (forked behind the status reset, joined on the host)
-    size_t run_piece_bytes = (size_t)16 << 20;  // upper bound; a run is cut into >= 4 pieces of >= 4 MiB (below)
-    bool piece_fixed = false;
-    if (const char* e = getenv("BU_RUN_PIECE_MIB")) {  // 0 disables the pieced pipeline
-        run_piece_bytes = (size_t)atoll(e) << 20;
-        piece_fixed = true;
-    }
-    for (size_t k = 0; k < n_img; k++) {
-        const bu_slice_desc& s = p.slices[p.first_slice[k]];
-        const bu_image& im = p.images[k];
-        if (im.size == 0) continue;
-        if (p.etc1s) {
-            // (launched once for the whole file above)
+    const char* const fixed_piece_mib = getenv("BU_RUN_PIECE_MIB");
+    const bu_target bt = bu_read_block_target(target);
+    for (const BuFileRun& r : l.runs) {
+        if (r.bytes == 0) continue;
+        const uint8_t* const src = file + r.file_ofs;
+        uint8_t* const d_run = d_in + r.in_off;
+        uint8_t* const d_run_out = d_out + p.images[r.first].offset;
+        const size_t piece_bytes = bu_run_piece_bytes(r.bytes, fixed_piece_mib);
+        const bool pieced = bu_run_is_pieced(target, direct_out, piece_bytes, r.bytes);
+        if (pieced) {
+            constexpr int n_ps = 2;  // streams that carry pieces: the context's internal one and one of its own
+            if ((st = bu_ctx_streams(ctx, n_ps - 1))) return st;
+            if (used_extra < n_ps - 1) {
+                BU_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));  // the status words are reset on the context stream
+                for (; used_extra < n_ps - 1; used_extra++) BU_HIP(ctx, hipStreamWaitEvent(ctx->extra_streams[used_extra], ctx->ev0, 0));
+            }
+            const size_t obytes = bu_target_block_bytes(bt);
+            size_t piece_no = 0;
+            for (size_t done = 0; done < r.bytes; done += piece_bytes, piece_no++) {
+                const size_t nbytes = r.bytes - done < piece_bytes ? r.bytes - done : piece_bytes;
+                const size_t lane = piece_no % (size_t)n_ps;
+                hipStream_t ps = lane ? ctx->extra_streams[lane - 1].load(std::memory_order_acquire) : ctx->stream;
+                BU_HIP(ctx, hipMemcpyAsync(d_run + done, src + done, nbytes, hipMemcpyHostToDevice, ps));
+                crc_enqueue(d_run + done, r.file_ofs + done, nbytes, ps);
+                if ((st = bu_launch_uastc(ctx, bt, d_run + done, nbytes / 16, d_run_out + (done / 16) * obytes, 1, done / 16, d_status + r.first, ps, BU_ZEROCOPY_GRID)))
+                    return st;
+            }
         } else {
-            size_t run_end = k;  // last image of the run starting at k (only evaluated for run leaders)
-            bool pieced = false;
-            if (run_of[k] == k) {
-                while (run_end + 1 < n_img && run_of[run_end + 1] == k) run_end++;
-                const size_t run_bytes = in_off[run_end] + p.slices[p.first_slice[run_end]].file_size - in_off[k];
-                // A large block-linear run with a mapped (page-locked) output: upload and transcode in pieces on two
-                // streams, so that piece i's results cross PCIe upstream while piece i+1 comes down.
-                // piece size: a quarter of the run, between 4 and 16 MiB (a 16 MiB file: 0.672 ms in one piece, 0.585 in four,
-                // 0.645 in eight -- tools/exp/file_time.py)
-                size_t piece_bytes = run_piece_bytes;
-                if (!piece_fixed) {
-                    piece_bytes = (run_bytes / 4) & ~(((size_t)1 << 20) - 1);
-                    if (piece_bytes < ((size_t)4 << 20)) piece_bytes = (size_t)4 << 20;
-                    if (piece_bytes > run_piece_bytes) piece_bytes = run_piece_bytes;
-                }
-                // (Round 6 tried the same pieces for a PAGEABLE output too -- four streams, upload and launch of a piece on one stream, shared launch shapes -- from
-                // runs of 64 MiB on: 2.64 against 2.52 ms for a 64 MiB file, 5.17 against 4.97 for 128 MiB, profiles/r06_read_to_pieces_pageable_output.txt.  The call is
-                // two PCIe copies long and the kernels are 1 % of it; with a pageable output the run stays one upload, one launch -- which draws its tiles by
-                // ticket from 2^24 blocks on -- and one download.)
-                if (target != BU_READ_RGBA && direct_out && piece_bytes && run_bytes >= 2 * piece_bytes) {
-                    pieced = true;
-                    constexpr int n_ps = 2;  // streams that carry pieces: the context's internal one and one of its own
-                    {
-                        const bu_status sst = bu_ctx_streams(ctx, n_ps - 1);
-                        if (sst) return sst;
-                    }
-                    if (used_extra < n_ps - 1) {
-                        BU_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));  // the status words are reset on the context stream
-                        for (; used_extra < n_ps - 1; used_extra++) BU_HIP(ctx, hipStreamWaitEvent(ctx->extra_streams[used_extra], ctx->ev0, 0));
-                    }
-                    const bu_target pbt = bu_read_block_target(target);
-                    const size_t obytes = bu_target_block_bytes(pbt);
-                    size_t piece_no = 0;
-                    for (size_t done = 0; done < run_bytes; done += piece_bytes, piece_no++) {
-                        const size_t nbytes = run_bytes - done < piece_bytes ? run_bytes - done : piece_bytes;
-                        const size_t lane = piece_no % (size_t)n_ps;
-                        hipStream_t ps = lane ? ctx->extra_streams[lane - 1].load(std::memory_order_acquire) : ctx->stream;
-                        BU_HIP(ctx, hipMemcpyAsync(d_in + in_off[k] + done, file + s.file_ofs + done, nbytes, hipMemcpyHostToDevice, ps));
-                        crc_enqueue(d_in + in_off[k] + done, (size_t)s.file_ofs + done, nbytes, ps);
-                        st = bu_launch_uastc(ctx, pbt, d_in + in_off[k] + done, nbytes / 16, d_out + im.offset + (done / 16) * obytes, 1, done / 16, d_status + k, ps,
-                                             BU_ZEROCOPY_GRID);
-                        if (st) return st;
-                    }
-                } else {
-                    BU_HIP(ctx, hipMemcpyAsync(d_in + in_off[k], file + s.file_ofs, run_bytes, hipMemcpyHostToDevice, ctx->stream));
-                    crc_enqueue(d_in + in_off[k], s.file_ofs, run_bytes, ctx->stream);
-                }
-            }
-            const bu_target bt = bu_read_block_target(target);
-            if (target == BU_READ_RGBA) {  // image geometry differs per slice: one launch each
-                st = bu_launch_uastc(ctx, bt, d_in + in_off[k], s.file_size / 16, d_out + im.offset, s.num_blocks_x ? s.num_blocks_x : 1, 0, d_status + k,
-                                     ctx->stream, direct_out ? BU_ZEROCOPY_GRID : 0);
-            } else if (run_of[k] == k && !pieced) {  // block-linear: the run's outputs are contiguous from im.offset on
-                const size_t run_bytes = in_off[run_end] + p.slices[p.first_slice[run_end]].file_size - in_off[k];
-                st = bu_launch_uastc(ctx, bt, d_in + in_off[k], run_bytes / 16, d_out + im.offset, 1, 0, d_status + k, ctx->stream,
-                                     direct_out ? BU_ZEROCOPY_GRID : 0);
-            }
+            BU_HIP(ctx, hipMemcpyAsync(d_run, src, r.bytes, hipMemcpyHostToDevice, ctx->stream));
+            crc_enqueue(d_run, r.file_ofs, r.bytes, ctx->stream);
         }
-        if (st) return st;
+        if (target == BU_READ_RGBA) {  // image geometry differs per slice: one launch each
+            for (size_t k = r.first; k <= r.last; k++) {
+                const bu_slice_desc& s = p.slices[p.first_slice[k]];
+                if ((st = bu_launch_uastc(ctx, bt, d_in + l.in_off[k], s.file_size / 16, d_out + p.images[k].offset, s.num_blocks_x ? s.num_blocks_x : 1, 0, d_status + k,
+                                          ctx->stream, direct_out ? BU_ZEROCOPY_GRID : 0)))
+                    return st;
+            }
+        } else if (!pieced) {  // block-linear: the run's outputs are contiguous from its first image's offset on
+            if ((st = bu_launch_uastc(ctx, bt, d_run, r.bytes / 16, d_run_out, 1, 0, d_status + r.first, ctx->stream, direct_out ? BU_ZEROCOPY_GRID : 0))) return st;
+        }
     }
     lap("reserve + enqueue");
     // the status words (and the CRC registers of the pieces) are read on the context stream: it must see the other streams' kernels.  Joined on the
@@ -813,44 +669,66 @@ static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const u
     BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     drain.armed = false;
     lap("download + synchronise");
-    if (crc_deferred) {  // fold the device's piece registers with the bytes only the host has seen, in file order
+    if (crc_deferred) {  // the reference checks the CRC before anything else behind the header (basis.rs:338-341): before the status words
         crc_deferred = false;
-        std::sort(crc_segs.begin(), crc_segs.end(), [](const CrcSeg& a, const CrcSeg& b) { return a.file_ofs < b.file_ofs; });
-        bool foldable = true;
-        size_t pos = 77;
-        for (const CrcSeg& g2 : crc_segs) {  // overlapping slices (a hostile slice table): the plain host CRC decides
-            if (g2.file_ofs < pos || g2.file_ofs + g2.len > len) foldable = false;
-            pos = g2.file_ofs + g2.len;
-        }
-        bool crc_ok;
-        if (!foldable) {
-            crc_ok = bu_host::crc16(file + 77, len - 77, 0) == crc_want;
-        } else {
-            const uint16_t shift_piece = bu_host::crc16_shift(1, BU_CRC_PIECE);  // x^(8 * 65536)
-            uint16_t reg = 0xFFFF;  // register of CRC-16/GENIBUS before the first payload byte
-            pos = 77;
-            for (const CrcSeg& g2 : crc_segs) {
-                reg = bu_host::crc16_raw(file + pos, g2.file_ofs - pos, reg);
-                for (size_t i = 0; i < g2.n_pieces; i++) reg = (uint16_t)(bu_host::crc16_gf_mul(reg, shift_piece) ^ crc_parts[g2.first_piece + i]);
-                const size_t covered = g2.n_pieces * BU_CRC_PIECE;
-                reg = bu_host::crc16_raw(file + g2.file_ofs + covered, g2.len - covered, reg);
-                pos = g2.file_ofs + g2.len;
-            }
-            reg = bu_host::crc16_raw(file + pos, len - pos, reg);
-            crc_ok = (uint16_t)~reg == crc_want;
-        }
+        const bool crc_ok = bu_crc_fold(file, len, crc_segs, crc_parts.data(), crc_want);
         lap("data CRC fold");
         if (!crc_ok) return BU_ERR_DATA_CRC;
     }
-    for (size_t k = 0; k < n_img; k++) {  // first Err (in slice order) aborts the whole call, like the `?` in the reference drivers
-        st = bu_status_word_decode(words[k], nullptr);
-        if (st) return st;
-    }
+    for (size_t k = 0; k < n_img; k++)  // first Err (in slice order) aborts the whole call, like the `?` in the reference drivers
+        if ((st = bu_status_word_decode(words[k], nullptr))) return st;
     return BU_OK;
-    };
-    return settle(rest());
 }
 
+// etc1s_six: the call is bu_read_file_to (bu_plan_file)
+static bu_status bu_read_to_impl(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, bu_basis_header* header_out, bu_image* images,
+                                size_t max_images, size_t* n_images, uint8_t* out, size_t out_bytes, bool etc1s_six = false)
+{
+    if (!ctx || !out) return BU_ERR_ARGUMENT;
+    BuLap lap{getenv("BU_TRACE") != nullptr};
+    // The reference checks the payload CRC before anything else behind the header (basis.rs:338-341), so a CRC failure takes precedence
+    // over every later error, and nothing is reported as success before it is known.  Two kinds of file defer it past the plan: large
+    // UASTC files (bu_read_uastc_runs: on the device) and ETC1S files of some size (bu_read_etc1s_streamed: on a pool thread beside the
+    // entropy decode).  A path that returns with the CRC still deferred -- an early error, the one-launch path -- has it settled on the host.
+    bool crc_deferred = false;
+    uint16_t crc_want = 0;
+    {
+        bu_basis_header h0;
+        if (file && len >= ((size_t)1 << 20) && bu_host::read_header(file, len, &h0) == BU_OK && h0.tex_format == 1 && target != BU_READ_UASTC) {
+            crc_deferred = true;
+            crc_want = h0.data_crc16;
+        }
+        if (file && len >= ((size_t)64 << 10) && !getenv("BU_ETC1S_ONE_LAUNCH") && bu_host::read_header(file, len, &h0) == BU_OK && h0.tex_format == 0) {
+            crc_deferred = true;
+            crc_want = h0.data_crc16;
+        }
+    }
+    auto settle = [&](bu_status s) {  // the status to report once the deferred CRC is known
+        if (crc_deferred) {
+            crc_deferred = false;
+            if (bu_host::crc16(file + 77, len - 77, 0) != crc_want) return BU_ERR_DATA_CRC;
+        }
+        return s;
+    };
+    BuFilePlan p;
+    bu_status st = bu_plan_file(target, file, len, p, !crc_deferred, etc1s_six);
+    lap("plan (parse + CRCs)");
+    if (st) return settle(st);
+    if (header_out) *header_out = p.h;
+    if (n_images) *n_images = p.images.size();
+    if (out_bytes < p.out_bytes || (images && p.images.size() > max_images)) return settle(BU_ERR_OUTPUT_SIZE);
+    if (images) std::copy(p.images.begin(), p.images.end(), images);
+    if (p.images.empty()) return settle(BU_OK);
+    if (!p.etc1s) return settle(target == BU_READ_UASTC ? bu_read_uastc_copy(file, p, out) : bu_read_uastc_runs(ctx, target, file, len, p, out, crc_deferred, crc_want, lap));
+    size_t total_blocks = 0;
+    for (size_t k = 0; k < p.images.size(); k++) total_blocks += (size_t)p.slices[p.first_slice[k]].num_blocks_x * p.slices[p.first_slice[k]].num_blocks_y;
+    if (total_blocks >= BU_ETC1S_STREAM_MIN_BLOCKS && !getenv("BU_ETC1S_ONE_LAUNCH")) {
+        const bool pending = crc_deferred;
+        crc_deferred = false;  // settled inside (on a pool thread); nothing is left for settle()
+        return bu_read_etc1s_streamed(ctx, target, file, len, p, out, pending, crc_want, lap);
+    }
+    return settle(bu_read_etc1s_one_launch(ctx, target, file, len, p, out, lap));
+}
 
 // C++ exceptions must not cross the C ABI (a ctypes or Rust caller would be terminated): vectors sized from untrusted
 // file fields can throw std::bad_alloc, thread creation std::system_error.  A file that asks for more memory than

@@ -809,12 +809,11 @@ __global__ void bu_status_reset_kernel(unsigned long long* words, unsigned n)
 // The CRC is linear over GF(2): register(A || B) = register(A) * x^(8|B|) + register(B).  One workgroup covers a 64 KiB piece:
 // every thread runs the table-driven register over its own 256 bytes (slicing by four, tables in LDS), multiplies it by
 // x^(8 * bytes behind it inside the piece) and the workgroup XORs the 256 contributions.  The host folds the pieces' registers
-// (and the few bytes the device never sees: slice table, gaps, tails) in file order -- bu_read_to.
+// (and the few bytes the device never sees: slice table, gaps, tails) in file order -- bu_crc_fold, bu_file_layout.hpp, which has BU_CRC_PIECE.
 struct BuCrcTables {
     uint16_t t[4][256];  // t[k][b]: register after byte b followed by k zero bytes
     uint16_t pw[256];    // pw[k] = x^(8 * 256 * k) mod P
 };
-constexpr unsigned BU_CRC_PIECE = 65536;
 
 __device__ __forceinline__ uint32_t bu_crc_gf_mul(uint32_t a, uint32_t b)  // a * b mod x^16 + x^12 + x^5 + 1
 {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bu_basis.hpp"
+#include "bu_file_layout.hpp"
 
 static uint64_t rng_state = 88172645463325252ull;
 static uint32_t rnd()
@@ -23,6 +24,33 @@ static uint32_t rnd()
     return (uint32_t)(rng_state >> 11);
 }
 
+// The index buffer and the slice table of whatever slice table the file has (csrc/bu_file_layout.hpp): every entry's indices lie inside the
+// buffer, and the kernels' lookup finds every unit in the entry of the image whose [unit0, unit0 + units_of) holds it (all units of a
+// table of ordinary size, the first and last of every entry of a hostile one that claims millions).
+static bu_status check_etc1s_layout(const bu_host::BuFilePlan& p)
+{
+    BuEtc1sFileLayout l;
+    const bu_status st = bu_etc1s_file_layout(p, l);
+    if (st) return st;
+    const uint32_t n = (uint32_t)(l.descs.size() - 1);
+    bool ok = l.descs.size() >= 1 && l.descs[n].unit0 == l.n_units && l.words <= 0xFFFFFFFFull;
+    const auto held = [&](uint32_t u) {
+        const BuEtc1sSlice& d = l.descs[bu_etc1s_unit_slice(l.descs.data(), n, u)];
+        return d.image < l.unit0.size() && l.unit0[d.image] <= u && u - l.unit0[d.image] < l.units_of[d.image];
+    };
+    for (uint32_t s = 0; ok && s < n; s++) {
+        const BuEtc1sSlice& d = l.descs[s];
+        ok = d.n_blocks && (size_t)d.idx_ofs + d.n_blocks <= l.words && (!p.alpha_pairs || (size_t)d.aidx_ofs + d.n_blocks <= l.words) &&
+             d.unit0 == l.unit0[d.image] && held(d.unit0) && held(d.unit0 + l.units_of[d.image] - 1);
+    }
+    for (uint32_t u = 0; ok && l.n_units <= 65536 && u < l.n_units; u++) ok = held(u);
+    if (!ok) {
+        fprintf(stderr, "the ETC1S layout of %zu images breaks an invariant\n", p.images.size());
+        abort();
+    }
+    return BU_OK;
+}
+
 // plan + (for ETC1S) full host decode of every slice, as bu_read_to does before any upload
 static int process(const uint8_t* f, size_t len, int target)
 {
@@ -30,6 +58,8 @@ static int process(const uint8_t* f, size_t len, int target)
     bu_status st = bu_host::bu_plan_file((bu_read_target)target, f, len, p);
     if (st) return st;
     if (!p.etc1s) return 0;
+    st = check_etc1s_layout(p);
+    if (st) return st;
     bu_host::BasisLz lz;
     st = bu_host::bu_make_lz(f, len, p.h, lz);
     if (st) return st;
