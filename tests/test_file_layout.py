@@ -86,13 +86,16 @@ def etc1s_files():
     return out
 
 
-@pytest.mark.parametrize("alpha", [True, False], ids=["alpha", "opaque"])
-@pytest.mark.parametrize("target", ["etc1", "rgba", "bc3"])
-def test_etc1s_layout_is_the_model(layout, etc1s_files, alpha, target):
-    read_target, six, block_bytes = {"etc1": (_lib.READ_ETC1, 0, 8), "rgba": (_lib.READ_RGBA, 0, 16), "bc3": (_lib.READ_BC3, 1, 16)}[target]
+ETC1S_TARGETS = {"etc1": (_lib.READ_ETC1, 0, 8), "rgba": (_lib.READ_RGBA, 0, 16), "bc3": (_lib.READ_BC3, 1, 16)}  # name -> (read target, six, block bytes)
+
+
+def check_etc1s_layout(layout, f, file_dims, alpha, target):
+    """the layout of the ETC1S file f (images of file_dims blocks, alpha: colour / alpha slice pairs) for `target` is the model's, and the kernel's
+    lookup over the produced table finds every unit's image -> (the layout, unit_slice: the table entry of every unit)"""
+    read_target, six, block_bytes = ETC1S_TARGETS[target]
     pairs = alpha and target != "etc1"  # ETC1 of a file with alpha: every slice is an image of its own
-    dims = DIMS if pairs or not alpha else [d for d in DIMS for _ in range(2)]
-    got = layout("etc1s", read_target, six, file=etc1s_files[alpha])
+    dims = file_dims if pairs or not alpha else [d for d in file_dims for _ in range(2)]
+    got = layout("etc1s", read_target, six, file=f)
     want = etc1s_model(dims, pairs, block_bytes, target == "rgba")
     unit_slice = got.pop("unit_slice")
     assert got == want
@@ -104,6 +107,13 @@ def test_etc1s_layout_is_the_model(layout, etc1s_files, alpha, target):
     spans = 2 if pairs else 1
     for d in got["descs"][:-1]:
         assert d[3] + d[1] <= got["words"] and (spans == 1 or d[4] + d[1] <= got["words"])
+    return got, unit_slice
+
+
+@pytest.mark.parametrize("alpha", [True, False], ids=["alpha", "opaque"])
+@pytest.mark.parametrize("target", list(ETC1S_TARGETS))
+def test_etc1s_layout_is_the_model(layout, etc1s_files, alpha, target):
+    check_etc1s_layout(layout, etc1s_files[alpha], DIMS, alpha, target)
 
 
 def test_etc1s_layout_that_does_not_fit_32_bits_is_out_of_bounds(layout):

@@ -6,6 +6,7 @@ import pytest
 
 import basis_builder as bb
 import basisu_rs_amd as bu
+import file_shape_cases as fsc
 from basisu_rs_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -61,6 +62,9 @@ def make_cases(golden):
     f = bb.etc1s_file(np.random.default_rng(7), [(181, 182)], n_codebook=1024)[0]
     assert len(f) < 64 << 10 and 181 * 182 >= 32768  # CRC up front, streamed
     cases["etc1s streamed, crc up front"] = ("rgba", f, [range(len(f) - 2000, len(f) - 1990)], {}, False)
+    f = fsc.etc1s_file("array_240", True)
+    assert len(f) >= 64 << 10 and fsc.total_blocks("array_240") >= 32768  # CRC deferred, streamed: on a pool thread beside 288 small slices
+    cases["etc1s streamed, crc deferred"] = ("rgba", f, [range(len(f) - 2000, len(f) - 1990)], {}, False)
     return cases
 
 
@@ -85,7 +89,7 @@ def read(ctx, target, f, pinned):
 
 
 @pytest.mark.parametrize("name", ["uastc, host crc", "uastc, device crc", "uastc, pieced", "etc1s one launch, crc up front", "etc1s one launch, crc deferred",
-                                  "etc1s streamed, crc up front"])
+                                  "etc1s streamed, crc up front", "etc1s streamed, crc deferred"])
 def test_driver_path(ctx, oracle, cases, monkeypatch, name):
     target, f, damage, env, pinned = cases[name]
     for k, v in env.items():

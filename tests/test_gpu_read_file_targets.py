@@ -8,6 +8,7 @@ import pytest
 
 import basis_builder as bb
 import test_etc1s_targets as tet
+from file_shape_cases import check_model as _check_model, tuples as _tuples, want_blocks as _want
 from basisu_rs_amd import (BasisuError, TargetTextureFormat, _lib, read_file_query, read_file_to, read_header, read_slice_descs, read_to_astc,
                            read_to_bc1, read_to_bc3, read_to_bc4, read_to_bc5, read_to_bc7, read_to_eac_r11, read_to_eac_rg11, read_to_etc1,
                            read_to_etc2, read_to_rgba, write_uastc_file)
@@ -17,38 +18,6 @@ NAMES = tuple(tet.TARGETS)
 # 4096 blocks: a whole number of 64-block units; 561: ends mid-unit and its units straddle rows; one block
 SMALL = [(64, 64), (33, 17), (1, 1)]
 STREAMED = [(192, 192), (33, 17), (1, 1)]  # 37 426 blocks per plane: above BU_ETC1S_STREAM_MIN_BLOCKS
-
-
-def _tuples(imgs):
-    return [(g.w, g.h, g.stride, g.data.tobytes()) for g in imgs]
-
-
-def _want(oracle, f, alpha):
-    """per image: (w, h, nbx, blocks [n, 64] of the oracle's RGBA32 read)"""
-    st, _, imgs = oracle.read_to("rgba", f)
-    assert st == 0
-    descs = read_slice_descs(f, read_header(f))
-    step = 2 if alpha else 1
-    assert len(imgs) * step == len(descs)
-    out = []
-    for k, (_, _, _, data) in enumerate(imgs):
-        d = descs[step * k]
-        nbx, nby = d.num_blocks_x, d.num_blocks_y
-        assert data.size == nbx * nby * 64
-        out.append((d.orig_width, d.orig_height, nbx, data.reshape(nby, 4, nbx, 4, 4).transpose(0, 2, 1, 3, 4).reshape(-1, 64)))  # image -> blocks
-    return out
-
-
-def _check_model(got, want, name):
-    bytes_per_block = tet.TARGETS[name][1]
-    assert len(got) == len(want)
-    for k, (g, (w, h, nbx, rgba)) in enumerate(zip(got, want)):
-        assert (g.w, g.h, g.stride) == (w, h, bytes_per_block * nbx), (name, k)
-        blocks = np.frombuffer(g.data.tobytes(), dtype=np.uint8).reshape(-1, bytes_per_block)
-        model = tet.model(name, rgba)
-        assert blocks.shape == model.shape, (name, k)
-        bad = np.nonzero((blocks != model).any(1))[0]
-        assert bad.size == 0, "%s image %d: %d blocks differ, first %d: %s vs %s" % (name, k, bad.size, bad[0], blocks[bad[0]], model[bad[0]])
 
 
 @pytest.fixture(scope="module")
