@@ -2,6 +2,13 @@
 config-4 path.  It writes the bitstream the reference *reads* (src/basis.rs:417-572,
 src/basis_lz/huffman.rs:43-184, src/basis_lz/mod.rs:188-608).  It makes random but always-valid symbol
 choices; what the symbols decode to is established by the oracle, and the product must agree with it.
+
+It also keeps a record of its own (SliceSymbols.indices): the (endpoint index, selector index) each block means, worked out on the
+ENCODER's side from the rules of mod.rs:244-455 and 610-656 while the symbols are chosen -- no decoder is called or imported here.
+Explicit Huffman tables (`tables=`, table_rule) and explicit streams (`script=`, SCRIPTS) write the legal files a fitted code
+over a random stream never is: empty, incomplete, 16-bit and over-subscribed tables, records that overshoot their symbol count,
+slices that are one long run.  Every existing call writes the bytes it always wrote: the new code draws nothing from the caller's
+rng unless a script is named.
 """
 import heapq
 import struct
@@ -101,11 +108,69 @@ class Coder:
         bw.put(self.codes[sym], self.lengths[sym])
 
 
+def lookup_table(lengths):
+    """the decoding table the reference builds (huffman.rs:133-174) -> (table: entry index -> symbol or -1, max code size, symbol -> code as written).
+    Symbols are filled in symbol order, each at every index whose low `size` bits are its bit-reversed canonical code -- the
+    code truncated to its size (huffman.rs:163) -- so in an over-subscribed length set a later symbol overwrites an earlier one."""
+    max_len = max(lengths, default=0)
+    count = [0] * 18
+    for ln in lengths:
+        count[ln] += 1
+    count[0] = 0
+    next_code = [0] * 18
+    total = 0
+    for bits in range(1, 17):
+        total = (total + count[bits - 1]) << 1
+        next_code[bits] = total
+    table = [-1] * (1 << max_len)
+    codes = {}
+    for sym, ln in enumerate(lengths):
+        if ln:
+            c = next_code[ln] & ((1 << ln) - 1)
+            next_code[ln] += 1
+            codes[sym] = int(format(c, "0%db" % ln)[::-1], 2)
+            table[codes[sym]::1 << ln] = [sym] * (1 << (max_len - ln))
+    return table, max_len, codes
+
+
+def kraft(lengths):
+    """Kraft sum of a length set in units of 2^-16 (65536 = a complete code)"""
+    return sum(1 << (16 - ln) for ln in lengths if ln)
+
+
+class LookupCoder:
+    """writes symbols of an explicit length set through the reference's lookup (lookup_table): a symbol may be written where every
+    entry its code reaches is still its own, whatever bits follow it (in a prefix code: always)"""
+
+    def __init__(self, lengths):
+        self.lengths = list(lengths)
+        self.table, self.max_len, self.codes = lookup_table(self.lengths)
+        self.owned = {}
+
+    def owns(self, sym):
+        """(entries of sym's code that still decode to sym, entries its code reaches)"""
+        if sym not in self.owned:
+            reach = self.table[self.codes[sym]::1 << self.lengths[sym]]
+            self.owned[sym] = (sum(1 for t in reach if t == sym), len(reach))
+        return self.owned[sym]
+
+    def put(self, bw, sym):
+        assert sym < len(self.lengths) and self.lengths[sym] > 0, "symbol %d has no code" % sym
+        mine, reach = self.owns(sym)
+        assert mine >= 1, "symbol %d owns no entry of the lookup" % sym
+        assert mine == reach, "symbol %d shares its code with a later symbol: the bits behind it would pick the entry" % sym
+        bw.put(self.codes[sym], self.lengths[sym])
+
+
 CL_ORDER = [17, 18, 19, 20, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15, 16]
 
 
-def write_huffman_table(bw, lengths, use_runs=True):
-    """Huffman table record (huffman.rs:43-118): symbol code sizes, themselves coded with the 21-symbol alphabet"""
+def write_huffman_table(bw, lengths, use_runs=True, total_used=None, tail=None, cl_lengths=None, cl_n=None):
+    """Huffman table record (huffman.rs:43-118): symbol code sizes, themselves coded with the 21-symbol alphabet.
+    total_used: the 14-bit symbol count to write instead of len(lengths) without its trailing zeros (the reader stops at the first
+    token that reaches it, huffman.rs:67); tail = ("zero" | "repeat", count): one more run token behind the lengths, which the
+    reader takes whole although it passes total_used (huffman.rs:73-112 push `count` sizes unconditionally); cl_lengths: the 21
+    code sizes of the code-length alphabet instead of fitted ones; cl_n: how many of them are written, in CL_ORDER"""
     n = len(lengths)
     while n > 1 and lengths[n - 1] == 0:
         n -= 1
@@ -131,15 +196,31 @@ def write_huffman_table(bw, lengths, use_runs=True):
         else:
             toks.append((v, None, 0))
             i += 1
+    if tail is not None:
+        kind, count = tail
+        if kind == "zero":
+            assert 3 <= count <= 138
+            toks.append((18, count - 11, 7) if count >= 11 else (17, count - 3, 3))
+        else:
+            assert kind == "repeat" and 3 <= count <= 134 and n and lengths[n - 1] != 0
+            toks.append((20, count - 7, 7) if count >= 7 else (19, count - 3, 2))
     freq = [0] * 21
     for t, _, _ in toks:
         freq[t] += 1
-    cl_len = huffman_lengths(freq, max_len=7)
+    if cl_lengths is not None:
+        cl_len = list(cl_lengths)
+        assert len(cl_len) == 21 and all(cl_len[t] for t, _, _ in toks)
+    else:
+        cl_len = huffman_lengths(freq, max_len=7) if toks else [0] * 21
     cl = Coder(cl_len)
-    bw.put(n, 14)
-    ncl = 21
-    while ncl > 1 and cl_len[CL_ORDER[ncl - 1]] == 0:
-        ncl -= 1
+    bw.put(n if total_used is None else total_used, 14)
+    if cl_n is None:
+        ncl = 21
+        while ncl > 1 and cl_len[CL_ORDER[ncl - 1]] == 0:
+            ncl -= 1
+    else:
+        ncl = cl_n
+        assert all(cl_len[CL_ORDER[k]] == 0 for k in range(ncl, 21))
     bw.put(ncl, 5)
     for k in range(ncl):
         bw.put(cl_len[CL_ORDER[k]], 3)
@@ -230,16 +311,67 @@ def encode_selectors(rows, raw=True):
     return bw.bytes()
 
 
-class SliceSymbols:
-    """random valid symbol stream of one slice (mod.rs:188-458), recorded first so code lengths can be fitted"""
+# name -> what replaces the random draws of SliceSymbols, per decision: pred (the 2 x 2 group symbol), delta (the delta-endpoint symbol),
+# sel (the selector symbol).  None = the random draw.  A few fixed behaviours, not a language:
+#   pred  all_delta     symbol 255 for every group: every block a delta
+#         one_run       the first group is symbol 147 (delta / left / up / diagonal: valid at every position), the second group starts ONE
+#                       repeat run (symbol 256, mod.rs:265-271) that lasts to the slice's last group
+#   delta const         always 1
+#         wrap          n_endpoints - 1 or - 2: the sum passes n_endpoints wherever the previous index is at least 2 (mod.rs:346-351)
+#   sel   const         always the literal n_selectors - 1
+#         no_rle        random literals and history hits, never the run symbol
+#         rle_const     random, every run has the run symbol 2
+#         one_run       block 0 the literal n_selectors - 1, block 1 starts ONE run of nbx*nby - 1 blocks through the 63-escape (mod.rs:386-388)
+#         run_exact_end block 0 that literal; a run of 5 blocks that ends on the slice's last block; otherwise as no_rle
+#         run_leftover  the same run with 40 blocks left over at the slice's end
+#         hist_last     max(1, hs // 2) literals, then every selector the history entry hs - 1 (mod.rs:403-419, 635-642)
+SCRIPTS = {
+    "pred_run": dict(pred="one_run"),
+    "sel_run": dict(sel="one_run"),
+    "one_run": dict(pred="one_run", sel="one_run"),
+    "run_exact_end": dict(sel="run_exact_end"),
+    "run_leftover": dict(sel="run_leftover"),
+    "hist_last": dict(sel="hist_last"),
+    "delta_wrap": dict(pred="all_delta", delta="wrap"),
+    "single_pred": dict(pred="all_delta"),
+    "single_delta": dict(delta="const"),
+    "single_sel": dict(sel="const"),
+    "single_rle": dict(sel="rle_const"),
+    "no_rle": dict(sel="no_rle"),
+}
+ONE_RUN_PRED_SYM = 3 | (0 << 2) | (1 << 4) | (2 << 6)  # 147
 
-    def __init__(self, rng, nbx, nby, n_endpoints, n_selectors, history_size, is_video=False, p_repeat=0.15, p_history=0.25, p_rle=0.05):
+
+class SliceSymbols:
+    """random (or scripted) valid symbol stream of one slice (mod.rs:188-458), recorded first so code lengths can be fitted.
+    indices[nby, nbx] = (endpoint index, selector index): what each block means, kept from the encoder's side while the symbols are
+    chosen -- the four endpoint predictors (mod.rs:301-355; the delta wraps once past n_endpoints, mod.rs:346-351; texture video's
+    predictor 2 reads the previous frame, which the reference zeroes per slice, mod.rs:236-237, 327-331, 428-431), the approximate
+    move-to-front selector history with its rover (mod.rs:402-427, 610-643) and both run forms (mod.rs:258-271, 372-396)"""
+
+    def __init__(self, rng, nbx, nby, n_endpoints, n_selectors, history_size, is_video=False, p_repeat=0.15, p_history=0.25, p_rle=0.05, script=None):
         self.ops = []  # (table, symbol) or ("vlc", value, bits)
         T_PRED, T_DELTA, T_SEL, T_RLE = 0, 1, 2, 3
+        sc = SCRIPTS[script] if isinstance(script, str) else (script or {})
+        s_pred, s_delta, s_sel = sc.get("pred"), sc.get("delta"), sc.get("sel")
         prev_sym = 0
         repeat = 0
         sel_rle = 0
         row_bits = [0] * nbx  # pred bits saved for the odd row below
+        # the record
+        self.indices = np.zeros((nby, nbx, 2), dtype=np.uint32)
+        self.wraps = [0] * nby          # delta sums that passed n_endpoints, per row
+        self.runs = []                  # (first block, blocks asked for) of every selector run
+        self.pred_runs = []             # (first group, groups) of every predictor repeat run
+        self.op_start = []              # per block, raster order: len(ops) before anything of the block (its group symbol included) was written
+        hist = [0] * history_size       # ApproxMoveToFront::new (mod.rs:616-621)
+        rover = history_size // 2
+        prev_ep = 0                     # mod.rs:228
+        above, cur_row = [0] * nbx, [0] * nbx
+        n_groups = ((nbx + 1) // 2) * ((nby + 1) // 2)
+        n_blocks = nbx * nby
+        group_no = 0
+        lits = 0
 
         def valid_pred(p, x, y):
             if p == 0:
@@ -256,13 +388,41 @@ class SliceSymbols:
                     return False
             return True
 
+        def start_run(block_no, total, escape):
+            """the run symbol at this block: the block and the total - 1 behind it repeat history entry 0 (mod.rs:380-396)"""
+            assert history_size > 0 and total >= 3
+            self.ops.append((T_SEL, n_selectors + history_size))
+            if escape:
+                self.ops.append((T_RLE, 63))
+                self.ops.append(("vlc", total - 3, 7))
+            else:
+                assert total - 3 < 63
+                self.ops.append((T_RLE, total - 3))
+            self.runs.append((block_no, total))
+            return total - 1
+
         cur_bits = 0
         for y in range(nby):
             for x in range(nbx):
+                block_no = y * nbx + x
+                self.op_start.append(len(self.ops))
                 if x % 2 == 0:
                     if y % 2 == 0:
                         if repeat:
                             repeat -= 1
+                            cur_bits = prev_sym
+                        elif s_pred == "all_delta" or (s_pred == "one_run" and (group_no == 0 or n_groups - 1 < 3)):
+                            sym = 255 if s_pred == "all_delta" else ONE_RUN_PRED_SYM
+                            self.ops.append((T_PRED, sym))
+                            cur_bits = sym
+                            prev_sym = sym
+                        elif s_pred == "one_run":
+                            assert group_no == 1
+                            count = n_groups - 1
+                            self.ops.append((T_PRED, 256))
+                            self.ops.append(("vlc", count - 3, 4))
+                            self.pred_runs.append((group_no, count))
+                            repeat = count - 1
                             cur_bits = prev_sym
                         else:
                             # how many upcoming groups (raster order over even rows) accept prev_sym?
@@ -277,6 +437,7 @@ class SliceSymbols:
                                 count = int(rng.integers(3, run + 1))
                                 self.ops.append((T_PRED, 256))
                                 self.ops.append(("vlc", count - 3, 4))
+                                self.pred_runs.append((group_no, count))
                                 repeat = count - 1
                                 cur_bits = prev_sym
                             else:
@@ -287,38 +448,163 @@ class SliceSymbols:
                                 self.ops.append((T_PRED, sym))
                                 cur_bits = sym
                                 prev_sym = sym
+                        group_no += 1
                         row_bits[x] = cur_bits >> 4
                     else:
                         cur_bits = row_bits[x]
                 pred = cur_bits & 3
                 cur_bits >>= 2
                 if pred == 3:
-                    self.ops.append((T_DELTA, int(rng.integers(0, n_endpoints))))
+                    if s_delta == "const":
+                        d = 1 % n_endpoints
+                    elif s_delta == "wrap":
+                        d = max(n_endpoints - 1 - (block_no & 1), 0)
+                    else:
+                        d = int(rng.integers(0, n_endpoints))
+                    self.ops.append((T_DELTA, d))
+                    e = prev_ep + d  # mod.rs:346-351
+                    if e >= n_endpoints:
+                        e -= n_endpoints
+                        self.wraps[y] += 1
+                elif pred == 0:
+                    e = prev_ep  # mod.rs:311
+                elif pred == 1:
+                    e = above[x]  # mod.rs:322-324
+                else:
+                    e = 0 if is_video else above[x - 1]  # mod.rs:327-338
+                cur_row[x] = e
+                prev_ep = e
+                sel = 0  # (texture video, predictor 2: the previous frame's selector, zero; no selector symbol, a run is not counted down)
                 if (not is_video) or pred != 2:
+                    kind = None  # ("lit", s) | ("hist", i); a run block reads history entry 0 without moving it (mod.rs:372-374, 415)
                     if sel_rle:
                         sel_rle -= 1
-                    else:
+                        sel = hist[0]
+                    elif s_sel is None or s_sel == "rle_const":
                         u = rng.random()
                         if history_size > 0 and u < p_rle:
-                            self.ops.append((T_SEL, n_selectors + history_size))
-                            if rng.random() < 0.2:
-                                extra = int(rng.integers(0, 300))
-                                self.ops.append((T_RLE, 63))
-                                self.ops.append(("vlc", extra, 7))
-                                sel_rle = 3 + extra - 1
+                            if s_sel == "rle_const":
+                                sel_rle = start_run(block_no, 5, False)
                             else:
-                                run_sym = int(rng.integers(0, 63))
-                                self.ops.append((T_RLE, run_sym))
-                                sel_rle = 3 + run_sym - 1
+                                self.ops.append((T_SEL, n_selectors + history_size))
+                                if rng.random() < 0.2:
+                                    extra = int(rng.integers(0, 300))
+                                    self.ops.append((T_RLE, 63))
+                                    self.ops.append(("vlc", extra, 7))
+                                    sel_rle = 3 + extra - 1
+                                else:
+                                    run_sym = int(rng.integers(0, 63))
+                                    self.ops.append((T_RLE, run_sym))
+                                    sel_rle = 3 + run_sym - 1
+                                self.runs.append((block_no, sel_rle + 1))
+                            sel = hist[0]
                         elif history_size > 0 and u < p_rle + p_history:
-                            self.ops.append((T_SEL, n_selectors + int(rng.integers(0, history_size))))
+                            kind = ("hist", int(rng.integers(0, history_size)))
                         else:
-                            self.ops.append((T_SEL, int(rng.integers(0, n_selectors))))
+                            kind = ("lit", int(rng.integers(0, n_selectors)))
+                    else:
+                        tail = min(5, n_blocks - 1)  # the run of run_exact_end / run_leftover: the slice's last `tail` blocks
+                        if s_sel == "const" or (block_no == 0 and s_sel in ("one_run", "run_exact_end", "run_leftover")):
+                            kind = ("lit", n_selectors - 1)
+                        elif s_sel == "one_run" and n_blocks - 1 >= 3:
+                            assert block_no == 1
+                            sel_rle = start_run(block_no, n_blocks - 1, True)
+                            sel = hist[0]
+                        elif s_sel in ("run_exact_end", "run_leftover") and tail >= 3 and block_no == n_blocks - tail:
+                            sel_rle = start_run(block_no, tail + (40 if s_sel == "run_leftover" else 0), False)
+                            sel = hist[0]
+                        elif s_sel == "hist_last":
+                            if lits < max(1, history_size // 2):
+                                kind = ("lit", n_selectors - 1 - lits % n_selectors)
+                                lits += 1
+                            else:
+                                kind = ("hist", history_size - 1)
+                        elif history_size > 0 and rng.random() < p_history:
+                            kind = ("hist", int(rng.integers(0, history_size)))
+                        else:
+                            kind = ("lit", int(rng.integers(0, n_selectors)))
+                    if kind is not None and kind[0] == "hist":
+                        hi = kind[1]
+                        self.ops.append((T_SEL, n_selectors + hi))
+                        sel = hist[hi]
+                        if hi:  # use_index: the entry changes places with the one half way to the front (mod.rs:635-642)
+                            hist[hi // 2], hist[hi] = hist[hi], hist[hi // 2]
+                    elif kind is not None:
+                        sel = kind[1]
+                        self.ops.append((T_SEL, sel))
+                        if history_size > 0:  # add (mod.rs:627-633): at the rover, which walks the back half
+                            hist[rover] = sel
+                            rover += 1
+                            if rover == history_size:
+                                rover = history_size // 2
+                self.indices[y, x] = (e, sel)
+            above, cur_row = cur_row, above
+        self.run_pending = sel_rle  # blocks of a selector run left over at the slice's end: the next slice starts without them (mod.rs:223)
 
 
-def encode_etc1s_payload(rng, slices_dims, n_endpoints, n_selectors, history_size=32, is_video=False):
-    """-> (tables_bytes, [slice_bytes...]) for slices of the given (nbx, nby)"""
-    streams = [SliceSymbols(rng, nbx, nby, n_endpoints, n_selectors, history_size, is_video) for nbx, nby in slices_dims]
+TABLE_NAMES = ("pred", "delta", "sel", "rle")
+
+
+def table_rule(rule, freqs):
+    """a named shape of one slice table over the symbol counts `freqs` -> dict(lengths=, total_used=, tail=) for write_huffman_table"""
+    used = [i for i, f in enumerate(freqs) if f > 0]
+    fitted = huffman_lengths(freqs) if used else []
+    n = max(used) + 1 if used else 0
+    if rule == "fitted":
+        return dict(lengths=fitted)
+    if rule == "single":  # one used symbol, length 1
+        assert len(used) == 1
+        return dict(lengths=fitted)
+    if rule in ("fixed16", "fixed8"):  # every used symbol the same length: incomplete unless exactly 2^length symbols are used
+        ln = int(rule[5:])
+        assert len(used) <= 1 << ln
+        return dict(lengths=[ln if f > 0 else 0 for f in freqs])
+    if rule == "incomplete":  # the fitted code, every length one more: Kraft sum 1/2 (1/4 for a single symbol)
+        assert max(fitted) < 16
+        return dict(lengths=[ln + 1 if ln else 0 for ln in fitted])
+    if rule == "long_tail_zero":  # ... | zero run of 12 from symbol n: 11 sizes past total_used = n + 1
+        return dict(lengths=fitted[:n], total_used=n + 1, tail=("zero", 12))
+    if rule == "long_tail_repeat":  # ... | repeat of 6 from symbol n: 5 sizes past total_used = n + 1, all of them coded symbols
+        # the six phantom symbols need room in the code: lengthen every code until they fit (the fitted code is complete)
+        for d in range(1, 16):
+            lengths = [ln + d if ln else 0 for ln in fitted[:n]]
+            if max(lengths) <= 16 and kraft(lengths + [lengths[-1]] * 6) <= 65536:
+                return dict(lengths=lengths, total_used=n + 1, tail=("repeat", 6))
+        raise AssertionError("no room for the repeated sizes")
+    if rule == "collide":
+        # Kraft sum above 1: the fitted (complete) code and one unused symbol more.  Taken is the first (symbol, length) after which
+        # every used symbol still owns every entry its code reaches (LookupCoder.put asserts it again symbol by symbol)
+        assert len(used) >= 2
+        for u in (i for i in range(len(freqs)) if freqs[i] == 0):
+            for ln in range(max(fitted), 0, -1):
+                lengths = list(fitted)
+                lengths[u] = ln
+                coder = LookupCoder(lengths)
+                if all(coder.owns(sym)[0] == coder.owns(sym)[1] for sym in used):
+                    return dict(lengths=lengths)
+        raise AssertionError("no colliding length set keeps every used symbol whole")
+    if rule == "empty":  # no symbol at all: never decoded from
+        assert not used
+        return dict(lengths=[], total_used=0, cl_n=0)
+    if rule == "empty_one":  # one symbol of length 0
+        assert not used
+        return dict(lengths=[0], total_used=1)
+    raise KeyError(rule)
+
+
+def cl_rule(rule, rec):
+    """the code-length alphabet of a table record: "full" = all 21 symbols coded and written (n = 21)"""
+    if rule == "full":
+        rec.update(cl_lengths=[5] * 21, cl_n=21)  # 21 codes of 5 bits: Kraft sum 21/32
+    else:
+        raise KeyError(rule)
+
+
+def encode_etc1s_payload(rng, slices_dims, n_endpoints, n_selectors, history_size=32, is_video=False, tables=None, script=None, want_indices=False):
+    """-> (tables_bytes, [slice_bytes...]) for slices of the given (nbx, nby); with want_indices also the per-slice records.
+    tables: {"pred" | "delta" | "sel" | "rle": a TABLE rule name, or dict(lengths= a list or a rule name, total_used=, tail=, cl=
+    "full", cl_lengths=, cl_n=)} for the slice tables that are not to be fitted; script: a name of SCRIPTS (or such a dict)"""
+    streams = [SliceSymbols(rng, nbx, nby, n_endpoints, n_selectors, history_size, is_video, script=script) for nbx, nby in slices_dims]
     sizes = [257, n_endpoints, n_selectors + history_size + 1, 64]
     freqs = [[0] * s for s in sizes]
     for st in streams:
@@ -327,14 +613,31 @@ def encode_etc1s_payload(rng, slices_dims, n_endpoints, n_selectors, history_siz
                 freqs[op[0]][op[1]] += 1
     coders = []
     bw = BitWriter()
-    for f in freqs:
-        if sum(f) == 0:
-            f[0] = 1
-        ln = huffman_lengths(f)
-        coders.append(Coder(ln))
-        write_huffman_table(bw, ln)
+    for name, f in zip(TABLE_NAMES, freqs):
+        spec = (tables or {}).get(name)
+        if spec is None:
+            if sum(f) == 0:
+                f[0] = 1
+            ln = huffman_lengths(f)
+            coders.append(Coder(ln))
+            write_huffman_table(bw, ln)
+            continue
+        spec = dict(lengths=spec) if isinstance(spec, str) else dict(spec)
+        cl = spec.pop("cl", None)
+        given = spec.pop("lengths", "fitted")
+        rec = table_rule(given, f) if isinstance(given, str) else dict(lengths=list(given))
+        rec.update(spec)
+        if cl is not None:
+            cl_rule(cl, rec)
+        full = list(rec["lengths"])  # the sizes the reader ends up with: the run token behind total_used is taken whole
+        if rec.get("tail"):
+            while len(full) > 1 and full[-1] == 0:
+                full.pop()
+            full += [0 if rec["tail"][0] == "zero" else full[-1]] * rec["tail"][1]
+        coders.append(LookupCoder(full))
+        write_huffman_table(bw, **rec)
     bw.put(history_size, 13)
-    tables = bw.bytes()
+    tables_bytes = bw.bytes()
     out = []
     for st in streams:
         b = BitWriter()
@@ -344,7 +647,9 @@ def encode_etc1s_payload(rng, slices_dims, n_endpoints, n_selectors, history_siz
             else:
                 coders[op[0]].put(b, op[1])
         out.append(b.bytes())
-    return tables, out
+    if want_indices:
+        return tables_bytes, out, streams
+    return tables_bytes, out
 
 
 def build_basis_file(tex_format, slices, flags=0, tex_type=0, total_endpoints=0, endpoint_cb=b"", total_selectors=0, selector_cb=b"",
@@ -407,9 +712,11 @@ def uastc_file(block_arrays, dims, pads=None, **kw):
     return build_basis_file(1, slices, **kw)
 
 
-def etc1s_file(rng, dims, n_codebook=256, history_size=32, alpha=False, raw_selectors=True, is_video=False, grayscale=False):
+def etc1s_file(rng, dims, n_codebook=256, history_size=32, alpha=False, raw_selectors=True, is_video=False, grayscale=False, tables=None, script=None,
+               want_indices=False):
     """random ETC1S file; total_endpoints == total_selectors (the reference passes total_selectors for both,
-    basis.rs:289-291).  With alpha, slices alternate colour / alpha."""
+    basis.rs:289-291).  With alpha, slices alternate colour / alpha.  tables, script: see encode_etc1s_payload.
+    -> (file, endpoints, selector rows), with want_indices also the SliceSymbols of every slice (their .indices: the record)"""
     from basisu_rs_amd import synth
 
     ep, rows = synth.etc1s_codebooks(n_codebook, n_codebook, seed=int(rng.integers(0, 1 << 30)))
@@ -418,15 +725,21 @@ def etc1s_file(rng, dims, n_codebook=256, history_size=32, alpha=False, raw_sele
     ecb = encode_endpoints(ep, grayscale)
     scb = encode_selectors(rows, raw=raw_selectors)
     all_dims = [d for d in dims for _ in range(2 if alpha else 1)]
-    tables, datas = encode_etc1s_payload(rng, all_dims, n_codebook, n_codebook, history_size, is_video)
+    tables, datas, streams = encode_etc1s_payload(rng, all_dims, n_codebook, n_codebook, history_size, is_video, tables=tables, script=script, want_indices=True)
     slices = []
     for i, ((nbx, nby), d) in enumerate(zip(all_dims, datas)):
         is_a = alpha and (i & 1)
         slices.append(dict(data=d, orig_w=min(4 * nbx, 65535), orig_h=min(4 * nby, 65535), nbx=nbx, nby=nby,  # (orig_* are u16 metadata, basis.rs:554-571)
                             image_index=i // (2 if alpha else 1), flags=1 if is_a else 0))
     flags = 1 | (4 if alpha else 0)
-    return build_basis_file(0, slices, flags=flags, tex_type=3 if is_video else 0, total_endpoints=n_codebook, endpoint_cb=ecb,
-                            total_selectors=n_codebook, selector_cb=scb, tables=tables, total_images=len(dims)), ep, rows
+    f = build_basis_file(0, slices, flags=flags, tex_type=3 if is_video else 0, total_endpoints=n_codebook, endpoint_cb=ecb,
+                         total_selectors=n_codebook, selector_cb=scb, tables=tables, total_images=len(dims))
+    return (f, ep, rows, streams) if want_indices else (f, ep, rows)
+
+
+def index_words(stream):
+    """a slice's record as the index words the decoders give: endpoint | selector << 16, raster order"""
+    return (stream.indices[:, :, 0] | (stream.indices[:, :, 1] << 16)).reshape(-1).astype(np.uint32)
 
 
 def reseal(file_bytes):

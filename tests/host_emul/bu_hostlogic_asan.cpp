@@ -52,7 +52,9 @@ static bu_status check_etc1s_layout(const bu_host::BuFilePlan& p)
 }
 
 // plan + (for ETC1S) full host decode of every slice, as bu_read_to does before any upload
-static int process(const uint8_t* f, size_t len, int target)
+// report: print, per slice, which form produced decode_slice's result (the fast loop, or the exact loop after the fast one refused) and
+// whether the two-thread form decoded it, gave up or was not allowed to start (split_ok() false) -- tests/test_lz_shape_cases.py reads it
+static int process(const uint8_t* f, size_t len, int target, bool report = false)
 {
     bu_host::BuFilePlan p;
     bu_status st = bu_host::bu_plan_file((bu_read_target)target, f, len, p);
@@ -62,6 +64,7 @@ static int process(const uint8_t* f, size_t len, int target)
     if (st) return st;
     bu_host::BasisLz lz;
     st = bu_host::bu_make_lz(f, len, p.h, lz);
+    if (report) printf("codebooks and tables: status=%d\n", (int)st);
     if (st) return st;
     // sequential, as the reference does it ...
     std::vector<std::vector<uint32_t>> seq(p.slices.size()), par(p.slices.size());
@@ -87,9 +90,10 @@ static int process(const uint8_t* f, size_t len, int target)
                 fprintf(stderr, "decode_slice differs from decode_slice_exact in slice %zu\n", k);
                 abort();
             }
+            bool fast_ok = false;
             if (s.num_blocks_x && s.num_blocks_y) {
                 std::atomic<uint32_t> rows{0};
-                const bool fast_ok = lz.decode_slice_fast(s.num_blocks_x, s.num_blocks_y, f + s.file_ofs, s.file_size, fa.data(), &rows);
+                fast_ok = lz.decode_slice_fast(s.num_blocks_x, s.num_blocks_y, f + s.file_ofs, s.file_size, fa.data(), &rows);
                 if (fast_ok && (ex_st != BU_OK || fa != ex)) {
                     fprintf(stderr, "decode_slice_fast accepts slice %zu and disagrees with the exact loop (status %d)\n", k, (int)ex_st);
                     abort();
@@ -102,8 +106,10 @@ static int process(const uint8_t* f, size_t len, int target)
                     }
                 }
             }
+            if (report) printf("slice %zu: decode_slice=%s status=%d\n", k, fast_ok ? "fast" : "exact", (int)seq_st);
         }
     }
+    if (report) printf("split_ok=%d\n", lz.split_ok() ? 1 : 0);
     // ... and on 4 threads, as bu_read_to does it (threading forced: these files are tiny): same status, same indices
     std::vector<bu_host::SliceJob> jobs;
     for (size_t k = 0; k < p.slices.size(); k++) {
@@ -125,6 +131,7 @@ static int process(const uint8_t* f, size_t len, int target)
             std::thread th([&] { res_ok = lz.slice_resolve(s.num_blocks_x, s.num_blocks_y, tok_ep.data(), tok_sel.data(), out.data(), rows_lexed, failed, &rows_done, nullptr); });
             const bool lex_ok = lz.slice_lex(s.num_blocks_x, s.num_blocks_y, f + s.file_ofs, s.file_size, tok_ep.data(), tok_sel.data(), rows_lexed, failed);
             th.join();
+            if (report) printf("slice %zu: two-thread=%s\n", k, lex_ok && res_ok ? "lex+resolve" : "gave-up");
             if (lex_ok && res_ok) {
                 // (slices behind the first failing one were never decoded by the sequential loop: nothing to compare with)
                 const bool have_seq = seq_decoded > k;
@@ -147,6 +154,19 @@ static int process(const uint8_t* f, size_t len, int target)
         for (size_t k = 0; k < p.slices.size(); k++)
             if (seq[k] != par[k]) {
                 fprintf(stderr, "parallel decode differs in slice %zu\n", k);
+                abort();
+            }
+    // ... and decode_slices with its defaults, as the one-launch path calls it: a file this small takes its sequential loop
+    for (size_t k = 0; k < p.slices.size(); k++) std::fill(par[k].begin(), par[k].end(), 0u);
+    const bu_status def_st = bu_host::decode_slices(lz, jobs);
+    if (def_st != seq_st) {
+        fprintf(stderr, "decode_slices status %d != sequential %d\n", (int)def_st, (int)seq_st);
+        abort();
+    }
+    if (!seq_st)
+        for (size_t k = 0; k < p.slices.size(); k++)
+            if (seq[k] != par[k]) {
+                fprintf(stderr, "decode_slices differs in slice %zu\n", k);
                 abort();
             }
     return seq_st;
@@ -194,7 +214,7 @@ int main(int argc, char** argv)
     while ((n = fread(buf, 1, sizeof buf, fp)) > 0) base.insert(base.end(), buf, buf + n);
     fclose(fp);
     int ok = 0, bad = 0;
-    if (process(base.data(), base.size(), BU_READ_RGBA) != 0) return 3;  // the pristine file must parse
+    if (process(base.data(), base.size(), BU_READ_RGBA, true) != 0) return 3;  // the pristine file must parse
     for (int it = 0; it < iters; it++) {
         std::vector<uint8_t> g = base;
         const int kind = rnd() % 4;

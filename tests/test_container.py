@@ -105,15 +105,17 @@ def test_read_query_geometry_matches_oracle(oracle, golden):
 @pytest.mark.parametrize("kw", [dict(), dict(alpha=True), dict(raw_selectors=False), dict(is_video=True), dict(grayscale=True),
                                 dict(history_size=0), dict(history_size=1), dict(history_size=64, n_codebook=3)])
 def test_basislz_host_decoder_matches_oracle(oracle, kw):
-    """the serial entropy decode (Huffman tables, codebooks, predictors, history, RLE) -- product C++ vs oracle C"""
+    """the serial entropy decode (Huffman tables, codebooks, predictors, history, RLE) -- product C++ vs oracle C, and both against the record the
+    test encoder keeps of what every block means (basis_builder.SliceSymbols.indices: no decoder's reading)"""
     rng = np.random.default_rng(hash(str(sorted(kw.items()))) & 0xFFFF)
     for trial in range(25):
         dims = [(int(rng.integers(1, 40)), int(rng.integers(1, 30))) for _ in range(3)]
         kw2 = dict(n_codebook=int(rng.integers(2, 300)))
         kw2.update(kw)
-        f, ep, rows = bb.etc1s_file(rng, dims, **kw2)
+        f, ep, rows, streams = bb.etc1s_file(rng, dims, want_indices=True, **kw2)
         h = bu.read_header(f)
         sd = bu.read_slice_descs(f, h)
+        assert len(sd) == len(streams)
         for si, s in enumerate(sd):
             st, oep, osel, oidx = oracle.lz_decode(f[h.endpoint_cb_file_ofs:h.endpoint_cb_file_ofs + h.endpoint_cb_file_size],
                                                    f[h.selector_cb_file_ofs:h.selector_cb_file_ofs + h.selector_cb_file_size],
@@ -123,6 +125,7 @@ def test_basislz_host_decoder_matches_oracle(oracle, kw):
             pep, psel, pidx = bu.basislz_decode(f, si)
             assert (pep == oep).all() and (psel == osel).all()
             assert (pidx == (oidx[:, 0].astype(np.uint32) | (oidx[:, 1].astype(np.uint32) << 16))).all()
+            assert (pidx == bb.index_words(streams[si])).all(), (trial, si)
         # the codebooks survive the round trip through the test encoder
         assert (pep == ep).all() and (psel[:, :4] == rows).all()
 
