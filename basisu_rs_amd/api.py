@@ -147,6 +147,22 @@ class Context:
         self._check(st, bad, self._DECODE_BLOCK_ERRORS)
         return out[: n * 64]
 
+    def encode_blocks(self, fmt, rgba, width, height, in_pitch=0, out=None):
+        """bu_rgba_encode_blocks: an RGBA8 image of width x height pixels, pixel rows in_pitch bytes apart (0 = 4 * width), -> the blocks of one of the
+        six formats with an encoder from texels (BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB, BC3_RGBA), ceil(width / 4) per row, tight (DESIGN.md
+        section 4.10).  Partial edge blocks repeat the last column and row.  `rgba` holds (height - 1) * in_pitch + 4 * width bytes at least."""
+        a = _as_u8(rgba)
+        w, h, pitch = int(width), int(height), int(in_pitch)
+        if w > 0 and h > 0 and a.size < (h - 1) * (pitch or 4 * w) + 4 * w:
+            raise ValueError("rgba holds fewer bytes than the image")
+        n = ((w + 3) // 4) * ((h + 3) // 4)
+        bb = _lib.BLOCK_BYTES.get(int(fmt), 16)
+        if out is None:
+            out = np.empty(max(n, 1) * bb, dtype=np.uint8)
+        st = self._lib.bu_rgba_encode_blocks(self._h, int(fmt), a.ctypes.data, w, h, pitch, out.ctypes.data, out.size)
+        self._check(st)
+        return out[: n * bb]
+
     def set_launch_policy(self, shared):
         """bu_context_set_launch_policy.  "auto" / None (the default of a new context) = BU_LAUNCH_AUTO: decided per call -- shared when the launch goes
         to one of the context's own streams and another of them has work in flight, exclusive otherwise; False = BU_LAUNCH_EXCLUSIVE: a large launch
@@ -277,6 +293,13 @@ class Context:
         st = self._lib.bu_blocks_decode_rgba_device(self._h, int(fmt), _ptr(d_blocks), int(n_blocks), _ptr(d_rgba), int(blocks_per_row), int(out_pitch_bytes),
                                                     int(block_index_base), _ptr(d_status), _stream_ptr(stream))
         self._check(st, None, self._DECODE_BLOCK_ERRORS)
+
+    def encode_blocks_device(self, fmt, d_rgba, width, height, d_blocks, in_pitch=0, out_pitch=0, stream=None):
+        """bu_rgba_encode_blocks_device: the device form of encode_blocks (torch tensors or raw pointers); only enqueues.  in_pitch = 0: pixel rows of
+        4 * width bytes; out_pitch = 0: block rows of ceil(width / 4) blocks, tight.  No block can fail, so there is no status word."""
+        st = self._lib.bu_rgba_encode_blocks_device(self._h, int(fmt), _ptr(d_rgba), int(width), int(height), int(in_pitch), _ptr(d_blocks), int(out_pitch),
+                                                    _stream_ptr(stream))
+        self._check(st)
 
     def transcode_device_sync(self, fmt, d_in, n_blocks, d_out, blocks_per_row=0, block_index_base=0):
         """bu_uastc_transcode_device_sync: a contiguous device-resident range, blocking; one exclusive launch, tile tickets on long walks.

@@ -1,0 +1,85 @@
+// extern "C": an RGBA8 image -> BC4, BC5, EAC R11, EAC RG11, BC1 or BC3 blocks (include/basisu_hip.h).
+// Part of the single translation unit bu_hip.hip (included there; not a stand-alone header).
+#pragma once
+
+namespace {
+
+using BuEncodeFn = decltype(&bu_encode_kernel<BU_TGT_BC1>);
+const BuEncodeFn bu_encode_kernels[BU_N_TARGETS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bu_encode_kernel<BU_TGT_BC4>, bu_encode_kernel<BU_TGT_BC5>,
+                                                    bu_encode_kernel<BU_TGT_R11>, bu_encode_kernel<BU_TGT_RG11>, nullptr, bu_encode_kernel<BU_TGT_BC1>, bu_encode_kernel<BU_TGT_BC3>};
+
+// a format bu_rgba_encode_blocks takes: one of the six with an encoder from texels (nothing outside the enumeration)
+bool bu_encode_format_ok(bu_target format) { return (int)format >= 0 && (unsigned)format < BU_N_TARGETS && bu_encode_kernels[format] != nullptr; }
+
+// 0 = the tight pitch `tight`; else a multiple of `unit` of at least `tight`.  False for a bad pitch.
+bool bu_encode_pitch(size_t given, size_t unit, size_t tight, size_t* pitch)
+{
+    *pitch = given ? given : tight;
+    return *pitch % unit == 0 && *pitch >= tight;
+}
+
+}  // namespace
+
+extern "C" {
+
+bu_status bu_rgba_encode_blocks_device(bu_context* ctx, bu_target format, const void* d_rgba, size_t width, size_t height, size_t in_pitch_bytes, void* d_blocks,
+                                       size_t out_pitch_bytes, void* stream)
+{
+    if (!bu_encode_format_ok(format) || !ctx) return BU_ERR_ARGUMENT;
+    const bool empty = width == 0 || height == 0;
+    if (!empty && (!d_rgba || !d_blocks)) return BU_ERR_ARGUMENT;
+    const size_t bb = bu_target_block_bytes(format);
+    if (reinterpret_cast<uintptr_t>(d_rgba) % 4 || reinterpret_cast<uintptr_t>(d_blocks) % bb) return BU_ERR_ARGUMENT;
+    const size_t nbx = bu_enc_blocks(width), nby = bu_enc_blocks(height);
+    if (nbx > BU_ENC_MAX_NBX) return BU_ERR_ARGUMENT;  // (in front of the pitches: 4 * width and nbx * bb cannot overflow below)
+    size_t in_pitch, out_pitch;
+    if (!bu_encode_pitch(in_pitch_bytes, 4, 4 * width, &in_pitch) || !bu_encode_pitch(out_pitch_bytes, bb, nbx * bb, &out_pitch)) return BU_ERR_ARGUMENT;
+    if (empty) return BU_OK;
+    if (nby > ((size_t)1 << 62) / nbx) return BU_ERR_ARGUMENT;  // (no such image exists: the block count stays a size_t)
+    const size_t n_blocks = nbx * nby;
+    hipLaunchKernelGGL(bu_encode_kernels[format], dim3(bu_grid_for(n_blocks, (unsigned)ctx->cu_count)), dim3(BU_WG), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_rgba), width, height, in_pitch, static_cast<uint8_t*>(d_blocks), (unsigned)nbx, n_blocks, out_pitch, ctx->d_tables);
+    BU_HIP(ctx, hipGetLastError());
+    return BU_OK;
+}
+
+// Staging, one launch and the download as bu_blocks_decode_rgba does them: a page-locked buffer is read or written by the kernel directly (where it is
+// aligned as the device form asks), pageable memory goes through the context's device buffers.  The image's last row ends at its last pixel.
+bu_status bu_rgba_encode_blocks(bu_context* ctx, bu_target format, const uint8_t* rgba, size_t width, size_t height, size_t in_pitch_bytes, uint8_t* out, size_t out_bytes)
+{
+    if (!bu_encode_format_ok(format) || !ctx) return BU_ERR_ARGUMENT;
+    const bool empty = width == 0 || height == 0;
+    if (!empty && (!rgba || !out)) return BU_ERR_ARGUMENT;
+    const size_t bb = bu_target_block_bytes(format), nbx = bu_enc_blocks(width), nby = bu_enc_blocks(height);
+    if (nbx > BU_ENC_MAX_NBX) return BU_ERR_ARGUMENT;
+    size_t in_pitch;
+    if (!bu_encode_pitch(in_pitch_bytes, 4, 4 * width, &in_pitch)) return BU_ERR_ARGUMENT;
+    if (empty) return BU_OK;
+    if (nby > ((size_t)1 << 62) / nbx || height > ((size_t)1 << 62) / in_pitch) return BU_ERR_ARGUMENT;
+    const size_t in_bytes = (height - 1) * in_pitch + 4 * width, need = nbx * nby * bb;
+    if (out_bytes < need) return BU_ERR_OUTPUT_SIZE;
+    std::lock_guard<std::mutex> g(ctx->lock);
+    BU_HIP(ctx, hipSetDevice(ctx->device));
+    bu_status st;
+    void *zin = nullptr, *zout = nullptr;
+    const bool map_in = bu_device_view(rgba, &zin) && reinterpret_cast<uintptr_t>(zin) % 4 == 0;
+    const bool map_out = bu_device_view(out, &zout) && reinterpret_cast<uintptr_t>(zout) % bb == 0;
+    if (!map_in) {
+        st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, in_bytes);
+        if (st) return st;
+    }
+    if (!map_out) {
+        st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, need);
+        if (st) return st;
+    }
+    BuDrain drain(ctx);
+    if (!map_in) BU_HIP(ctx, hipMemcpyAsync(ctx->d_in, rgba, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = bu_rgba_encode_blocks_device(ctx, format, map_in ? zin : ctx->d_in, width, height, in_pitch, map_out ? zout : ctx->d_out, 0, ctx->stream);
+    if (st) return st;
+    if (!map_out) BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, need, hipMemcpyDeviceToHost, ctx->stream));
+    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    drain.armed = false;
+    return BU_OK;
+}
+
+}  // extern "C"

@@ -37,6 +37,7 @@
 #include "bu_uastc_dispatch.hpp"
 #include "bu_etc1s_targets.hpp"   // ETC1S per block: index check, ETC1, RGBA32, BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 (palette form)
 #include "bu_decode_blocks.hpp"   // block decoders: the ten block formats -> 16 RGBA8 texels
+#include "bu_encode_blocks.hpp"   // block encoders from pixels: 16 RGBA8 texels -> BC4 / BC5 / EAC R11 / RG11 / BC1 / BC3, and the gather of a block's texels
 #include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 #include "bu_rect_plan.hpp"    // rectangles of slices into pitched surfaces: job table, address mapping, launch plan
 #include "bu_etc1s_rect_plan.hpp"  // the same for ETC1S slices: 64-block units, a wave each
@@ -46,6 +47,7 @@
 #include "bu_kernels.hpp"        // device code: UASTC, status reset, CRC, sleep, copy
 #include "bu_etc1s_kernels.hpp"  // device code: the ETC1S back end
 #include "bu_decode_kernels.hpp" // device code: blocks -> RGBA8 image
+#include "bu_encode_kernels.hpp" // device code: RGBA8 image -> blocks
 #include "bu_context.hpp"        // bu_context, launcher, host-pointer driver
 #include "bu_streams.hpp"        // the context's own streams (hardware-queue check), BU_LAUNCH_AUTO
 #include "bu_capi_slice.hpp"     // extern "C": slice level
@@ -53,3 +55,4 @@
 #include "bu_capi_measure.hpp"   // extern "C": measurement helpers
 #include "bu_multi.hpp"          // extern "C": multi-GPU
 #include "bu_capi_decode.hpp"    // extern "C": blocks of the ten block formats -> RGBA8
+#include "bu_capi_encode.hpp"    // extern "C": an RGBA8 image -> blocks of the six formats with an encoder from texels

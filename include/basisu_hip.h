@@ -407,6 +407,32 @@ bu_status bu_blocks_decode_rgba_device(bu_context* ctx, bu_target format, const 
 bu_status bu_blocks_decode_rgba(bu_context* ctx, bu_target format, const uint8_t* blocks, size_t blocks_bytes,
                                 size_t blocks_per_row, uint8_t* out, size_t out_bytes, uint64_t* first_bad_block);
 
+/* ---- pixels to block formats ------------------------------------------------
+ * The remaining direction: an RGBA8 image that is already on the device -- a decoded atlas that was edited or composited, a rendered or
+ * generated texture, a tensor -- to blocks.
+ *   format   BU_TARGET_BC4_R, BC5_RG, EAC_R11, EAC_RG11, BC1_RGB or BC3_RGBA: the six formats whose encoder is a rule on 16 texels; any other
+ *            value (ASTC, BC7, ETC1, ETC2, RGBA32, the non-targets 5, 10, 13, negative values) is BU_ERR_ARGUMENT with nothing launched.
+ *   Geometry: width and height are in pixels, any value >= 1; nbx = ceil(width / 4), nby = ceil(height / 4).  Pixel (px, py) is the four bytes
+ *   R, G, B, A at d_rgba + py * in_pitch_bytes + 4 * px.  Texel (x, y) of block (bx, by) is pixel (min(4 bx + x, width - 1),
+ *   min(4 by + y, height - 1)): partial edge blocks repeat the last column and row.  Block (bx, by) is written at
+ *   d_blocks + by * out_pitch_bytes + bx * bu_target_block_bytes(format).  in_pitch_bytes is 0 (= 4 * width) or a multiple of 4 of at least
+ *   4 * width; out_pitch_bytes is 0 (= nbx * block bytes) or a multiple of the block size of at least nbx * block bytes.
+ *   Bytes: the block is exactly what bu_uastc_transcode to `format` writes for a UASTC block whose RGBA32 unpack is these 16 texels -- the rules
+ *   of DESIGN.md sections 4.4 / 4.5, unchanged: X = R and Y = A for the two-channel formats, BC1 drops A, BC3 = BC4 of A followed by BC1.  No
+ *   block can fail, so there is no status word.
+ *   Reads and writes: no byte outside [row, row + 4 * width) of pixel rows 0 .. height - 1 is read, so the result does not depend on pitch
+ *   padding; nothing outside the nbx * block bytes of each of the nby output rows is written.
+ * Device form: only enqueues on `stream` -- nothing is allocated, copied or synchronised, so it may be captured into a graph.  BU_ERR_ARGUMENT, with
+ * nothing launched, for: a format outside the six; a null context; a null buffer with a non-empty image; d_rgba not aligned to 4; d_blocks not
+ * aligned to the block size (8 or 16); a bad pitch; nbx above 2^28.  width == 0 or height == 0 is BU_OK and launches nothing; null buffers are
+ * allowed then, every other rule above still applies (an empty image with a bad format, alignment or pitch is BU_ERR_ARGUMENT).  An image whose base and pitch are multiples of 16 is read with 16-byte loads; any other with 4-byte loads, slower.
+ * Host form: staging, one launch and the download as bu_blocks_decode_rgba (page-locked buffers of bu_host_alloc are read / written directly);
+ * `rgba` holds (height - 1) * pitch + 4 * width bytes, the output is tight; BU_ERR_OUTPUT_SIZE when out_bytes < nbx * nby * block bytes. */
+bu_status bu_rgba_encode_blocks_device(bu_context* ctx, bu_target format, const void* d_rgba, size_t width, size_t height,
+                                       size_t in_pitch_bytes, void* d_blocks, size_t out_pitch_bytes, void* stream);
+bu_status bu_rgba_encode_blocks(bu_context* ctx, bu_target format, const uint8_t* rgba, size_t width, size_t height,
+                                size_t in_pitch_bytes, uint8_t* out, size_t out_bytes);
+
 /* ---- whole-file level: the crate's public read_to_* API (src/lib.rs:20-22, src/basis.rs) -------------
  * Host side in C++ (container parse, CRC-16, BasisLZ entropy decode -- byte/symbol serial, stays on the CPU),
  * block work on the GPU through the entry points above. */

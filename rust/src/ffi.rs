@@ -240,4 +240,9 @@ extern "C" {
                                                stream: *mut c_void) -> c_int;
     pub(crate) fn bu_blocks_decode_rgba(ctx: *mut bu_context, format: c_int, blocks: *const u8, blocks_bytes: usize, blocks_per_row: usize,
                                         out: *mut u8, out_bytes: usize, first_bad_block: *mut u64) -> c_int;
+    // an RGBA8 image -> blocks of the six formats with an encoder from texels (tests/test_gpu_encode_blocks.py; `encode_blocks` / `encode_blocks_device` of lib.rs)
+    pub(crate) fn bu_rgba_encode_blocks_device(ctx: *mut bu_context, format: c_int, d_rgba: *const c_void, width: usize, height: usize,
+                                               in_pitch_bytes: usize, d_blocks: *mut c_void, out_pitch_bytes: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn bu_rgba_encode_blocks(ctx: *mut bu_context, format: c_int, rgba: *const u8, width: usize, height: usize, in_pitch_bytes: usize,
+                                        out: *mut u8, out_bytes: usize) -> c_int;
 }
