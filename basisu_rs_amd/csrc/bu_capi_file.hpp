@@ -123,36 +123,13 @@ static unsigned bu_etc1s_file_slot(const BuFilePlan& p, bu_read_target target)
     return p.etc1s_six ? bu_etc1s_target_slot(bu_read_block_target(target)) : target == BU_READ_RGBA ? 1u : 0u;
 }
 
-// BU_TRACE: the time since the previous lap, one line per step of a call
-struct BuLap {
-    const bool on;
-    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
-    void operator()(const char* what)
-    {
-        if (!on) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[bu_read_to] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-        t_prev = t;
-    }
-};
-
 // ---- streamed ETC1S front door -------------------------------------------------------------------------------------------------
-// A slice's symbol stream is serial (one host core: 1.86 ms of BASELINE config 4's 2.6), and everything else used to queue up in
-// front of and behind it: payload CRC 0.12 ms, codebooks 0.19 ms, upload + kernel + download 0.4 ms.  Here they run BESIDE it:
-//   * the slice loop needs the four Huffman tables and the codebook SIZES, never the codebook entries: the tables are parsed first
-//     (tens of microseconds), then pool threads decode the codebooks, run the payload CRC and decode the slices, all at once;
-//   * the decoders write their indices into a page-locked buffer the kernels read directly over PCIe (no upload), and publish
-//     finished block rows; the calling thread launches the whole-file kernel over each band of finished 64-block units, so the
-//     band's results travel to the (page-locked) output while the next rows are decoded.
-// Errors keep the reference's order: CRC (basis.rs:338-341) before codebooks (mod.rs:69-76) before tables (:77-83) before slices
-// (first failing slice in file order); work already launched for a file that fails is drained and its output discarded.
-constexpr size_t BU_ETC1S_STREAM_MIN_BLOCKS = 32768, BU_ETC1S_BAND_BLOCKS = 16384;
-
+// The device half of a streamed read: buffers up, the slices decoded and their bands launched by the scheduler of bu_etc1s_stream.hpp (which
+// says why and in what order) through a sink of this context's stream, results and status words down.
 static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, const uint8_t* file, size_t len, const BuFilePlan& p, uint8_t* out,
                                         bool crc_pending, uint16_t crc_want, BuLap& lap)
 {
     using bu_host::in_file;
-    const bool trace = lap.on;
     const bu_basis_header& h = p.h;
     // (the pool is not taken yet: the pooled CRC)
     const auto leave = [&](bu_status s) { return (crc_pending && bu_host::crc16(file + 77, len - 77, 0) != crc_want) ? BU_ERR_DATA_CRC : s; };
@@ -167,8 +144,6 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     BuEtc1sFileLayout l;
     bu_status st = bu_etc1s_file_layout(p, l);
     if (st) return leave(st);
-    const std::vector<BuEtc1sSlice>& descs = l.descs;
-    const std::vector<uint32_t>&unit0 = l.unit0, &units_of = l.units_of;
 
     std::lock_guard<std::mutex> g(ctx->lock);
     BU_HIP(ctx, hipSetDevice(ctx->device));
@@ -183,309 +158,53 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
         BU_HIP(ctx, hipHostMalloc(&ctx->h_idx, cap, hipHostMallocDefault));
         ctx->h_idx_cap = cap;
     }
-    uint32_t* const h_idx = static_cast<uint32_t*>(ctx->h_idx);
     void* d_idx_view = nullptr;
-    if (!bu_device_view(h_idx, &d_idx_view)) return BU_ERR_HIP;
+    if (!bu_device_view(ctx->h_idx, &d_idx_view)) return BU_ERR_HIP;
     void* zout = nullptr;
     const bool direct_out = bu_device_view(out, &zout);
     if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
     const size_t n_cb = h.total_selectors;
     const size_t ep_bytes = bu_align256(n_cb * 4), sel_bytes = bu_align256(n_cb * 8), status_bytes = bu_align256(8 * n_img),
-                 desc_bytes = bu_align256(descs.size() * sizeof(BuEtc1sSlice));
+                 desc_bytes = bu_align256(l.descs.size() * sizeof(BuEtc1sSlice));
     if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + 256))) return st;
     uint8_t* const aux = static_cast<uint8_t*>(ctx->d_aux);
     uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
     uint64_t* const d_status = reinterpret_cast<uint64_t*>(aux + ep_bytes + sel_bytes);
     const BuEtc1sSlice* const d_descs = reinterpret_cast<const BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
     BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes + sel_bytes + status_bytes, descs.data(), descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
+    BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes + sel_bytes + status_bytes, l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
     lap("reserve");
 
-    // ---- the jobs: [codebooks] [payload CRC] [slices ...] pulled from one counter by the pool threads ----
-    // A slice of BU_ETC1S_STREAM_MIN_BLOCKS blocks and more is decoded on TWO threads (bu_host::BasisLz::slice_lex / slice_resolve):
-    // one walks the bit stream and leaves a token pair per block, the other turns tokens into indices one row behind (endpoint
-    // prediction, selector history, the stores the GPU reads) -- the symbol loop of a slice is bound by one host core's instruction
-    // throughput, and this takes a quarter off it (1.55 -> 1.2 ms end to end for BASELINE config 4).  Token buffers live in the
-    // context.  Any irregularity ends both halves, and whichever of the two finishes second decodes the slice again with the ordinary
-    // loops, which decide the status.
-    struct Job {
-        size_t nbx = 0, nby = 0;
-        const uint8_t* data = nullptr;
-        size_t len = 0;
-        uint32_t* idx = nullptr;
-        std::atomic<uint32_t> rows{0};
-        std::atomic<int> done{0};
-        bu_status st = BU_OK;
-        // the two-thread form
-        bool split = false;
-        uint32_t* tok_ep = nullptr;
-        uint16_t* tok_sel = nullptr;
-        std::atomic<uint32_t> rows_lexed{0};
-        std::atomic<bool> split_failed{false};
-        std::atomic<int> halves_done{0};
-        bool lex_ok = false, res_ok = false;
-    };
-    const size_t per_img = p.alpha_pairs ? 2 : 1;
-    std::vector<Job> jobs(n_img * per_img);
-    const bool may_split = st_tables == BU_OK && lz.split_ok() && !getenv("BU_ETC1S_ONE_THREAD");
-    size_t tok_bytes = 0;
-    for (size_t k = 0; k < n_img; k++)
-        for (size_t a = 0; a < per_img; a++) {
-            const bu_slice_desc& s = p.slices[p.first_slice[k] + a];
-            Job& j = jobs[k * per_img + a];
-            j.nbx = s.num_blocks_x;
-            j.nby = s.num_blocks_y;
-            j.data = file + s.file_ofs;
-            j.len = s.file_size;
-            j.idx = h_idx + (a ? l.aidx_ofs[k] : l.idx_ofs[k]);
-            if (may_split && j.nbx * j.nby >= BU_ETC1S_STREAM_MIN_BLOCKS) {
-                j.split = true;
-                tok_bytes += (j.nbx * j.nby * 6 + 127) & ~(size_t)63;
-            }
-        }
+    // the token buffer of the two-thread slices lives in the context (no memory for it: the ordinary loop)
+    const bool may_split = bu_etc1s_may_split(st_tables, lz, !getenv("BU_ETC1S_ONE_THREAD"));
+    const size_t tok_bytes = bu_etc1s_stream_tok_bytes(p, may_split);
     if (tok_bytes > ctx->lex_cap) {
         free(ctx->lex_buf);
         ctx->lex_cap = 0;
         ctx->lex_buf = malloc(tok_bytes + tok_bytes / 4);
         if (ctx->lex_buf) ctx->lex_cap = tok_bytes + tok_bytes / 4;
     }
-    {
-        uint8_t* t = static_cast<uint8_t*>(ctx->lex_buf);
-        for (Job& j : jobs) {
-            if (!j.split) continue;
-            if (!t) {  // (no memory for the tokens: the ordinary loop)
-                j.split = false;
-                continue;
-            }
-            const size_t nblk = j.nbx * j.nby;
-            j.tok_ep = reinterpret_cast<uint32_t*>(t);
-            j.tok_sel = reinterpret_cast<uint16_t*>(t + nblk * 4);
-            t += (nblk * 6 + 127) & ~(size_t)63;
-        }
-    }
-    // abort: nothing that is still running can matter any more (a codebook / table / device error, or this function is on its way
-    // out): decoders stop at the next row.  slice_failed: some slice failed -- the feeder stops launching, but the OTHER slices
-    // decode on: the call reports the first failing slice in file order, and an earlier slice may still fail too.
-    std::atomic<bool> abort{false}, slice_failed{false}, feeder_taken{false};
-    std::atomic<int> cb_done{0};
-    bu_status st_cb = BU_OK, st_feed = BU_OK;
-    bool crc_ok = true;
-    // Who does what: the CALLING thread starts on the first slice at once (all of it, or its bit-serial half) -- the symbol stream
-    // of the (first) slice is the critical path, and a parked pool thread takes tens of microseconds to wake up.  The pool threads
-    // pull work items from one counter, in this order: the first slice's resolver half (its lexer is already running), the codebooks,
-    // the feeder role (it launches bands of finished units on the context stream until everything is launched), the payload
-    // CRC, then the other slices -- a two-thread slice as two items, lexer first, so that whoever pulls a resolver item knows its
-    // lexer has been claimed by a thread that never waits for anything.  The calling thread joins the queue when its own slice is
-    // done; if no pool thread ever took the feeder role it runs it last, when everything is decoded.
-    const uint32_t n_cb0 = (uint32_t)n_cb;
-    auto launch = [&](uint32_t u0, uint32_t u1) -> bu_status {
+    BuEtc1sSink sink;
+    sink.bind = [&]() -> bu_status {
+        BU_HIP(ctx, hipSetDevice(ctx->device));
+        return BU_OK;
+    };
+    sink.codebooks = [&](const bu_host::BasisLz& z) -> bu_status {
+        if (!z.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, z.endpoints.data(), z.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!z.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, z.selectors.data(), z.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
+        return BU_OK;
+    };
+    sink.launch = [&](uint32_t u0, uint32_t u1) -> bu_status {
         const unsigned grid = bu_grid_for((size_t)(u1 - u0) * 64, ctx->cu_count);
-        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(descs.size() - 1), u0, u1,
-                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), n_cb0, d_out, d_status);
+        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(l.descs.size() - 1), u0, u1,
+                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), (uint32_t)n_cb, d_out, d_status);
         BU_HIP(ctx, hipGetLastError());
         return BU_OK;
     };
-    auto feeder = [&]() -> bu_status {
-        BU_HIP(ctx, hipSetDevice(ctx->device));  // (a pool thread has no current device yet)
-        for (unsigned spin = 0; !cb_done.load(std::memory_order_acquire); spin++) {
-            if (abort.load(std::memory_order_relaxed)) return BU_OK;
-            if (spin > 64) std::this_thread::yield();
-        }
-        if (st_cb != BU_OK || st_tables != BU_OK) return BU_OK;  // (reported by the caller, in the reference's order)
-        if (!lz.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, lz.endpoints.data(), lz.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (!lz.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, lz.selectors.data(), lz.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
-        std::vector<uint32_t> launched(n_img, 0);  // units of image k already handed to the GPU
-        for (unsigned spin = 0;; spin++) {
-            bool all = true, progressed = false;
-            for (size_t k = 0; k < n_img; k++) {
-                if (units_of[k] == 0 || launched[k] == units_of[k]) continue;
-                // finished units of image k: whole 64-block units inside the rows BOTH of its slices have finished
-                uint32_t avail = units_of[k];
-                bool finished = true;
-                for (size_t a2 = 0; a2 < per_img; a2++) {
-                    Job& j = jobs[k * per_img + a2];
-                    if (j.done.load(std::memory_order_acquire)) continue;
-                    finished = false;
-                    const size_t blocks = (size_t)j.rows.load(std::memory_order_acquire) * j.nbx;
-                    avail = std::min<uint32_t>(avail, (uint32_t)(blocks / 64));
-                }
-                if (avail > launched[k] && (finished || (size_t)(avail - launched[k]) * 64 >= BU_ETC1S_BAND_BLOCKS)) {
-                    const bu_status ls = launch(unit0[k] + launched[k], unit0[k] + avail);
-                    if (ls) return ls;
-                    launched[k] = avail;
-                    progressed = true;
-                }
-                if (launched[k] != units_of[k]) all = false;
-            }
-            if (all || abort.load(std::memory_order_relaxed) || slice_failed.load(std::memory_order_relaxed)) return BU_OK;
-            if (!progressed && spin > 16) std::this_thread::yield();
-        }
-    };
-    // (a job runs on a pool thread: an exception -- std::bad_alloc from a vector sized by a hostile file -- must become a status there,
-    // it cannot unwind through the pool)
-    // publish_rows = false: the slice is decoded AGAIN after a two-thread attempt gave up (settle_split).  The resolver has already published
-    // rows -- final ones, which this pass writes again with the same values -- and the feeder may have launched bands over them: the row
-    // counter must not fall back to 1 and climb a second time, so this pass publishes nothing and the feeder picks the rest up from `done`.
-    auto run_slice = [&](Job& j, bool publish_rows = true) {
-        if (st_tables == BU_OK && !abort.load(std::memory_order_relaxed)) {
-            try {
-                j.st = lz.decode_slice(j.nbx, j.nby, j.data, j.len, j.idx, publish_rows ? &j.rows : nullptr, &abort);
-            } catch (...) {
-                j.st = BU_ERR_BOUNDS;
-            }
-        } else
-            j.st = BU_ERR_ARGUMENT;  // never reported: an earlier error decides
-        if (j.st) slice_failed.store(true, std::memory_order_relaxed);
-        j.done.store(1, std::memory_order_release);
-    };
-    // the halves of a two-thread slice; the one that finishes second settles the slice
-    auto settle_split = [&](Job& j) {
-        if (j.halves_done.fetch_add(1, std::memory_order_acq_rel) != 1) return;
-        if (j.lex_ok && j.res_ok) {
-            j.st = BU_OK;
-            j.done.store(1, std::memory_order_release);
-        } else {
-            run_slice(j, false);  // an irregular stream (or an abort): the ordinary loops, from the slice's first bit
-        }
-    };
-    auto run_lex = [&](Job& j) {
-        try {
-            j.lex_ok = lz.slice_lex(j.nbx, j.nby, j.data, j.len, j.tok_ep, j.tok_sel, j.rows_lexed, j.split_failed);
-        } catch (...) {
-            j.lex_ok = false;
-        }
-        if (!j.lex_ok) j.split_failed.store(true, std::memory_order_release);
-        settle_split(j);
-    };
-    auto run_resolve = [&](Job& j) {
-        try {
-            j.res_ok = lz.slice_resolve(j.nbx, j.nby, j.tok_ep, j.tok_sel, j.idx, j.rows_lexed, j.split_failed, &j.rows, &abort);
-        } catch (...) {
-            j.res_ok = false;
-        }
-        if (!j.res_ok) j.split_failed.store(true, std::memory_order_release);
-        settle_split(j);
-    };
-    // the work items behind the calling thread's own start on slice 0
-    enum ItemKind { I_RESOLVE, I_FEED, I_CODEBOOKS, I_CRC, I_SLICE, I_LEX };
-    struct Item {
-        ItemKind kind;
-        size_t job;
-    };
-    std::vector<Item> items;
-    if (!jobs.empty() && jobs[0].split) items.push_back({I_RESOLVE, 0});
-    items.push_back({I_CODEBOOKS, 0});
-    items.push_back({I_FEED, 0});
-    items.push_back({I_CRC, 0});
-    for (size_t k = 1; k < jobs.size(); k++) {
-        if (jobs[k].split) {
-            items.push_back({I_LEX, k});
-            items.push_back({I_RESOLVE, k});
-        } else
-            items.push_back({I_SLICE, k});
-    }
-    std::atomic<size_t> next{0};
-    const std::thread::id caller = std::this_thread::get_id();
-    // BU_TRACE: when every item started and ended, relative to this point
-    struct ItemLog {
-        double t0 = 0, t1 = 0;
-    };
-    std::vector<ItemLog> item_log(trace ? items.size() + 1 : 0);
-    const auto t_items = std::chrono::steady_clock::now();
-    auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_items).count(); };
-    const std::function<void()> work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < items.size();) {
-            const Item it = items[i];
-            struct Stamp {
-                ItemLog* l;
-                decltype(since)& now;
-                Stamp(ItemLog* l_, decltype(since)& n) : l(l_), now(n)
-                {
-                    if (l) l->t0 = now();
-                }
-                ~Stamp()
-                {
-                    if (l) l->t1 = now();
-                }
-            } stamp(trace ? &item_log[i] : nullptr, since);
-            switch (it.kind) {
-            case I_FEED: {
-                // (the calling thread leaves the role to a pool thread: it would stop pulling items for as long as bands are pending;
-                // it runs the feeder itself at the very end if nobody else did)
-                if (std::this_thread::get_id() == caller || feeder_taken.exchange(true)) break;
-                bu_status fs;
-                try {
-                    fs = feeder();
-                } catch (...) {
-                    fs = BU_ERR_HIP;
-                }
-                if (fs) {
-                    st_feed = fs;
-                    abort.store(true, std::memory_order_relaxed);
-                }
-                return;  // everything is launched (or stopped): nothing is left that this thread should start on
-            }
-            case I_CODEBOOKS:  // the first kernel launch waits for them
-                try {
-                    st_cb = lz.init_codebooks(file + h.endpoint_cb_file_ofs, h.endpoint_cb_file_size, file + h.selector_cb_file_ofs, h.selector_cb_file_size);
-                } catch (...) {
-                    st_cb = BU_ERR_BOUNDS;
-                }
-                if (st_cb) abort.store(true, std::memory_order_relaxed);
-                cb_done.store(1, std::memory_order_release);
-                break;
-            case I_CRC:
-                // (the serial form: bu_host::crc16 cuts large inputs into pieces for the pool -- which this call is holding)
-                if (crc_pending) crc_ok = (uint16_t)~bu_host::crc16_raw(file + 77, len - 77, 0xFFFF) == crc_want;
-                break;
-            case I_SLICE: run_slice(jobs[it.job]); break;
-            case I_LEX: run_lex(jobs[it.job]); break;
-            case I_RESOLVE: run_resolve(jobs[it.job]); break;
-            }
-        }
-    };
-    const unsigned helpers = bu_host::pool().begin((unsigned)std::min<size_t>(items.size(), bu_host::Pool::capacity()), work);
-    (void)helpers;
-    struct PoolEnd {  // the pool is released on every path out of this function, after the jobs have seen the abort flag
-        std::atomic<bool>& abort;
-        bool armed = true;
-        ~PoolEnd()
-        {
-            if (armed) {
-                abort.store(true);
-                bu_host::pool().end();
-            }
-        }
-    } pool_end{abort};
-    if (!jobs.empty()) {
-        if (jobs[0].split) run_lex(jobs[0]);
-        else run_slice(jobs[0]);
-    }
-    lap(!jobs.empty() && jobs[0].split ? "slice 0 lexed (resolver on a pool thread)" : "slice 0 decoded");
-    work();  // whatever is still in the queue (the feeder item is skipped by this thread)
-    pool_end.armed = false;
-    bu_host::pool().end();  // every item has finished; the feeder, if a pool thread took the role, has launched everything (or seen a flag)
-    if (!feeder_taken.exchange(true)) {  // nobody fed the GPU meanwhile: everything is decoded, launch it now
-        try {
-            st_feed = feeder();
-        } catch (...) {
-            st_feed = BU_ERR_HIP;
-        }
-    }
-    lap("pool joined, bands launched");
-    if (trace) {
-        static const char* const names[] = {"resolve", "feed", "codebooks", "crc", "slice", "lex"};
-        for (size_t i = 0; i < items.size(); i++)
-            fprintf(stderr, "[bu_read_to]   item %2zu %-9s job %2zu (%5zu x %5zu)  %7.3f .. %7.3f ms\n", i, names[items[i].kind], items[i].job,
-                    items[i].kind >= I_SLICE || items[i].kind == I_RESOLVE ? jobs[items[i].job].nbx : (size_t)0,
-                    items[i].kind >= I_SLICE || items[i].kind == I_RESOLVE ? jobs[items[i].job].nby : (size_t)0, item_log[i].t0, item_log[i].t1);
-    }
-    if (crc_pending && !crc_ok) return BU_ERR_DATA_CRC;
-    if (st_cb) return st_cb;
-    if (st_tables) return st_tables;
-    if (st_feed) return st_feed;  // (a device error: it stopped the decoders, whose statuses mean nothing then)
-    for (const Job& j : jobs)
-        if (j.st) return j.st;
+    BuEtc1sStreamResult res;
+    bu_etc1s_stream(file, len, p, l, lz, st_tables, crc_pending, crc_want, static_cast<uint32_t*>(ctx->h_idx), ctx->lex_buf, ctx->lex_cap, may_split, sink, lap, res);
+    if ((st = bu_etc1s_stream_status(crc_pending, st_tables, res))) return st;
+
     BU_HIP(ctx, hipMemcpyAsync(status_words.data(), d_status, 8 * n_img, hipMemcpyDeviceToHost, ctx->stream));
     if (p.out_bytes && !direct_out) BU_HIP(ctx, hipMemcpyAsync(out, d_out, p.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     BU_HIP(ctx, hipStreamSynchronize(ctx->stream));

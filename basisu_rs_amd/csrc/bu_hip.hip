@@ -43,6 +43,7 @@
 #include "bu_etc1s_rect_plan.hpp"  // the same for ETC1S slices: 64-block units, a wave each
 #include "bu_multi_addr.hpp"   // the multi-run launch: run cursor, tile corner, lane offsets (one copy for the kernel and the host tests)
 #include "bu_file_layout.hpp"  // whole files: ETC1S index buffer and slice table, UASTC runs and pieces, the CRC fold (host only)
+#include "bu_etc1s_stream.hpp" // whole ETC1S files, streamed: the scheduler of decoders and feeder behind a device sink (host only)
 
 #include "bu_kernels.hpp"        // device code: UASTC, status reset, CRC, sleep, copy
 #include "bu_etc1s_kernels.hpp"  // device code: the ETC1S back end

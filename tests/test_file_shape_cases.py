@@ -4,6 +4,7 @@ table -- 37 and 145 entries, images smaller than a unit, last units part empty -
 without UBSan, against that module's layout model."""
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -19,14 +20,30 @@ IDS = ["%s-%s" % (name, "alpha" if alpha else "opaque") for name, alpha in CASES
 def test_constants_are_pinned_to_the_source():
     """a changed threshold fails here instead of silently moving a shape to the other door or CRC mode"""
     src = open(os.path.join(CSRC, "bu_capi_file.hpp")).read()
-    m = re.search(r"constexpr size_t BU_ETC1S_STREAM_MIN_BLOCKS = (\d+), BU_ETC1S_BAND_BLOCKS = (\d+);", src)
-    assert m and (int(m.group(1)), int(m.group(2))) == (fsc.STREAM_MIN_BLOCKS, fsc.BAND_BLOCKS)
+    sched = open(os.path.join(CSRC, "bu_etc1s_stream.hpp")).read()  # the scheduler of the streamed door: the constants and the two rules that are functions
+    m = re.findall(r"constexpr size_t BU_ETC1S_STREAM_MIN_BLOCKS = (\d+), BU_ETC1S_BAND_BLOCKS = (\d+);", src + sched)
+    assert len(m) == 1 and (int(m[0][0]), int(m[0][1])) == (fsc.STREAM_MIN_BLOCKS, fsc.BAND_BLOCKS) and "BU_ETC1S_BAND_BLOCKS = " in sched
     # the two places that name the streamed door's threshold: the deferred CRC of an ETC1S file, and the choice of the door by the file's total blocks
     defer = re.findall(r"len >= \(\(size_t\)(\d+) << (\d+)\) && !getenv\(\"BU_ETC1S_ONE_LAUNCH\"\) && [^\n]*tex_format == 0", src)
     assert len(defer) == 1 and int(defer[0][0]) << int(defer[0][1]) == fsc.CRC_DEFER_BYTES
     assert len(re.findall(r"total_blocks >= BU_ETC1S_STREAM_MIN_BLOCKS && !getenv\(\"BU_ETC1S_ONE_LAUNCH\"\)", src)) == 1
-    assert len(re.findall(r"\(avail - launched\[k\]\) \* 64 >= BU_ETC1S_BAND_BLOCKS", src)) == 1
-    assert len(re.findall(r"j\.nbx \* j\.nby >= BU_ETC1S_STREAM_MIN_BLOCKS", src)) == 1  # the two-thread decode of a slice
+    # the band rule and the two-thread decode of a slice are functions now, each with one caller in the scheduler and the constant as its default: the host
+    # build of the scheduler (tests/host_emul/bu_etc1s_stream_check.cpp) answers with the shipped defaults at both sides of the module's numbers
+    assert len(re.findall(r"bu_etc1s_band_due\(avail, launched\[k\], finished, band_blocks\)", sched)) == 1
+    assert len(re.findall(r"size_t band_blocks = BU_ETC1S_BAND_BLOCKS\)", sched)) == 2  # the rule's default and the scheduler's, which it hands down
+    assert len(re.findall(r"bu_etc1s_slice_splits\(may_split, nblk, split_min\)", sched)) == 1  # (the job table; the token size asks per slice too)
+    assert len(re.findall(r"size_t split_min = BU_ETC1S_STREAM_MIN_BLOCKS[,)]", sched)) == 3  # the rule, the token size and the scheduler
+    he = os.path.join(ROOT, "tests", "host_emul")
+    subprocess.run(["make", "-C", he, "bu_etc1s_stream_asan"], check=True, capture_output=True)
+
+    def rule(*args):
+        return int(subprocess.run([os.path.join(he, "bu_etc1s_stream_asan"), "--rule"] + [str(a) for a in args], check=True, capture_output=True, text=True).stdout)
+
+    band_units = fsc.BAND_BLOCKS // fsc.UNIT
+    assert fsc.BAND_BLOCKS % fsc.UNIT == 0
+    # unfinished image: a band from BAND_BLOCKS blocks on, wherever it starts; finished: whatever is left; nothing new: nothing
+    assert [rule("band", 7 + band_units - 1, 7, 0), rule("band", 7 + band_units, 7, 0), rule("band", 8, 7, 1), rule("band", 7, 7, 1)] == [0, 1, 1, 0]
+    assert [rule("split", fsc.STREAM_MIN_BLOCKS - 1), rule("split", fsc.STREAM_MIN_BLOCKS)] == [0, 1]
 
 
 @pytest.mark.parametrize("name, alpha", CASES, ids=IDS)
