@@ -1,4 +1,4 @@
-// Host-side layout of the whole-file calls (bu_capi_file.hpp): where the slices of a planned file (BuFilePlan, bu_basis.hpp) go in the staged input, what the
+// Host-side layout of the whole-file calls (bu_capi_file.hpp): where the slices of a planned file (BuFilePlan, bu_container.hpp) go in the staged input, what the
 // whole-file ETC1S kernels are told about them, how a UASTC run is cut into pieces, and the fold of the device's CRC piece registers.  Pure arithmetic
 // over file fields -- the code that faces a hostile slice table.  No HIP in here: tests/host_emul/bu_emul_file_layout.cpp compiles it as it is and
 // tests/test_file_layout.py checks it without a GPU.
@@ -145,7 +145,7 @@ inline bool bu_run_is_pieced(bu_read_target target, bool mapped_out, size_t piec
 
 // ---- the payload CRC from the device's piece registers ------------------------------------------------------------------------------
 // bu_crc16_pieces_kernel (bu_kernels.hpp) leaves one register per whole BU_CRC_PIECE bytes of an uploaded range, each from a zero register.
-// The CRC is linear (bu_basis.hpp: crc16), so the payload's register is folded in file order from those and from the bytes only the host
+// The CRC is linear (bu_container.hpp: crc16), so the payload's register is folded in file order from those and from the bytes only the host
 // has seen: slice table, gaps, the tail of a range behind its last whole piece.
 constexpr unsigned BU_CRC_PIECE = 65536;
 struct BuCrcSeg {

@@ -197,6 +197,50 @@ static int pool_stress(int rounds)
     return 0;
 }
 
+// The fast slice loops' bit window (bu_host::BitWindow) against the exact loop's BitReader, bit for bit: random byte strings of 0 .. 40
+// bytes (shorter than one 8-byte load, and long enough for both the load and the byte tail), a random sequence of take(1 .. 17) with a
+// refill whenever fewer than 17 bits are held, and of vlc(4) / vlc(7) including the "more than 32 bits" refusal, read on to 64 bits and
+// more past the end: the zeros there are what the fuzz only reaches indirectly.  Every fourth string is all ones, whose vlc's all refuse.
+static void bit_window_check(int strings)
+{
+    long refusals = 0;
+    for (int s = 0; s < strings; s++) {
+        const size_t len = rnd() % 41;
+        uint8_t* bytes = (uint8_t*)malloc(len ? len : 1);  // exact size: ASan sees any over-read
+        for (size_t i = 0; i < len; i++) bytes[i] = (s & 3) == 3 ? 0xFF : (uint8_t)rnd();
+        bu_host::BitWindow w(bytes, len);
+        bu_host::BitReader r(bytes, len);
+        for (size_t used = 0; used < 8 * len + 64;) {
+            const unsigned op = rnd() % 8;
+            if (op < 6) {
+                const unsigned n = 1 + rnd() % 17;
+                if (w.have < 17) w.refill();
+                const uint32_t got = w.take(n), want = r.read(n);
+                if (got != want) {
+                    fprintf(stderr, "BitWindow::take(%u) = %u, BitReader::read = %u at bit %zu of %zu bytes\n", n, got, want, used, len);
+                    abort();
+                }
+                used += n;
+            } else {
+                const unsigned chunk = op == 6 ? 4 : 7;
+                uint32_t got = 0, want = 0;
+                const bool got_ok = w.vlc(chunk, &got), want_ok = bu_host::BasisLz::vlc(r, chunk, &want);
+                if (got_ok != want_ok || (got_ok && got != want)) {
+                    fprintf(stderr, "BitWindow::vlc(%u) = %d %u, BasisLz::vlc = %d %u at bit %zu of %zu bytes\n", chunk, (int)got_ok, got, (int)want_ok, want, used, len);
+                    abort();
+                }
+                refusals += !got_ok;
+                used += chunk + 1;  // (at least)
+            }
+        }
+        free(bytes);
+    }
+    if (!refusals) {
+        fprintf(stderr, "no vlc refused in %d strings\n", strings);
+        abort();
+    }
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 3 && !strcmp(argv[1], "--pool-stress")) {
@@ -205,6 +249,7 @@ int main(int argc, char** argv)
         return st;
     }
     if (argc < 3) return 2;
+    bit_window_check(4000);
     const int iters = atoi(argv[2]);
     FILE* fp = fopen(argv[1], "rb");
     if (!fp) return 2;

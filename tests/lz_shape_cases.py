@@ -17,7 +17,7 @@ fitted; tables "delta" and "rle" in a file with alpha pairs):
                     have, 8 being the first code size in the alphabet's order (huffman.rs:52-56)
   collide           Kraft sum above 1.  NOT a file that decodes: huffman.rs:143-149 makes next_code[16] = 65 536 x the Kraft sum of the sizes below 16, every
                     16-bit symbol adds one, and huffman.rs:176-178 refuses the table when any next_code exceeds 65 536 -- exactly when the Kraft sum
-                    exceeds 1.  So the symbol-order fill "later symbols overwrite" (huffman.rs:155-174; bu_basis.hpp's over-subscribed branch) is only ever
+                    exceeds 1.  So the symbol-order fill "later symbols overwrite" (huffman.rs:155-174; bu_huffman.hpp's over-subscribed branch) is only ever
                     the prelude of an error.  The case is written through that fill all the same (basis_builder.LookupCoder), and what is held is that the
                     oracle and the product refuse it with the same status.
   empty_rle         the history_rle table with total_used = 0 (and n = 0), and with total_used = 1 and the size 0, for history_size 0 and 32, in a stream
