@@ -32,8 +32,8 @@ bu_status bu_blocks_decode_rgba_device(bu_context* ctx, bu_target format, const 
     return BU_OK;
 }
 
-// Staging, one launch and the download as bu_uastc_decode_to_rgba does them (bu_uastc_host): a page-locked buffer is read or written by the
-// kernel directly, pageable memory goes through the context's device buffers.
+// A staged call (bu_staged_call.hpp) of one launch: a page-locked buffer is read or written by the kernel directly, pageable memory goes
+// through the context's device buffers.
 bu_status bu_blocks_decode_rgba(bu_context* ctx, bu_target format, const uint8_t* blocks, size_t blocks_bytes, size_t blocks_per_row, uint8_t* out,
                                 size_t out_bytes, uint64_t* first_bad_block)
 {
@@ -44,31 +44,15 @@ bu_status bu_blocks_decode_rgba(bu_context* ctx, bu_target format, const uint8_t
     if (n % blocks_per_row != 0) return BU_ERR_ARGUMENT;
     if (out_bytes / 64 < n) return BU_ERR_OUTPUT_SIZE;
     if (n == 0) return BU_OK;
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
+    BuStagedCall call(ctx, 1);
     bu_status st;
-    void *zin = nullptr, *zout = nullptr;
-    const bool map_in = bu_device_view(blocks, &zin), map_out = bu_device_view(out, &zout);
-    if (!map_in) {
-        st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, blocks_bytes);
-        if (st) return st;
-    }
-    if (!map_out) {
-        st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, n * 64);
-        if (st) return st;
-    }
-    uint64_t word = 0;
-    BuDrain drain(ctx);
-    if (!map_in) BU_HIP(ctx, hipMemcpyAsync(ctx->d_in, blocks, blocks_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemsetAsync(ctx->d_status, 0xFF, sizeof(uint64_t), ctx->stream));
-    st = bu_blocks_decode_rgba_device(ctx, format, map_in ? zin : ctx->d_in, n, map_out ? zout : ctx->d_out, blocks_per_row, 0, 0,
-                                      reinterpret_cast<uint64_t*>(ctx->d_status), ctx->stream);
-    if (st) return st;
-    BU_HIP(ctx, hipMemcpyAsync(&word, ctx->d_status, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    if (!map_out) BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
-    return bu_status_word_decode(word, first_bad_block);
+    const void* d_blocks = nullptr;
+    void* d_rgba = nullptr;
+    if ((st = call.begin()) || (st = call.output(out, n * 64, n * 64, true, 16, &d_rgba)) || (st = call.input(blocks, blocks_bytes, true, 16, &d_blocks)) ||
+        (st = call.status_reset()) ||
+        (st = bu_blocks_decode_rgba_device(ctx, format, d_blocks, n, d_rgba, blocks_per_row, 0, 0, call.d_status, ctx->stream)) || (st = call.finish()))
+        return st;
+    return call.status(first_bad_block);
 }
 
 }  // extern "C"

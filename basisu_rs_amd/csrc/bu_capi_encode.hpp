@@ -43,8 +43,8 @@ bu_status bu_rgba_encode_blocks_device(bu_context* ctx, bu_target format, const 
     return BU_OK;
 }
 
-// Staging, one launch and the download as bu_blocks_decode_rgba does them: a page-locked buffer is read or written by the kernel directly (where it is
-// aligned as the device form asks), pageable memory goes through the context's device buffers.  The image's last row ends at its last pixel.
+// A staged call (bu_staged_call.hpp) of one launch: a page-locked buffer is read or written by the kernel directly (where it is aligned as the
+// device form asks), pageable memory goes through the context's device buffers.  The image's last row ends at its last pixel.
 bu_status bu_rgba_encode_blocks(bu_context* ctx, bu_target format, const uint8_t* rgba, size_t width, size_t height, size_t in_pitch_bytes, uint8_t* out, size_t out_bytes)
 {
     if (!bu_encode_format_ok(format) || !ctx) return BU_ERR_ARGUMENT;
@@ -58,28 +58,14 @@ bu_status bu_rgba_encode_blocks(bu_context* ctx, bu_target format, const uint8_t
     if (nby > ((size_t)1 << 62) / nbx || height > ((size_t)1 << 62) / in_pitch) return BU_ERR_ARGUMENT;
     const size_t in_bytes = (height - 1) * in_pitch + 4 * width, need = nbx * nby * bb;
     if (out_bytes < need) return BU_ERR_OUTPUT_SIZE;
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
+    BuStagedCall call(ctx, 0);  // (an encoder has nothing to refuse: no status word)
     bu_status st;
-    void *zin = nullptr, *zout = nullptr;
-    const bool map_in = bu_device_view(rgba, &zin) && reinterpret_cast<uintptr_t>(zin) % 4 == 0;
-    const bool map_out = bu_device_view(out, &zout) && reinterpret_cast<uintptr_t>(zout) % bb == 0;
-    if (!map_in) {
-        st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, in_bytes);
-        if (st) return st;
-    }
-    if (!map_out) {
-        st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, need);
-        if (st) return st;
-    }
-    BuDrain drain(ctx);
-    if (!map_in) BU_HIP(ctx, hipMemcpyAsync(ctx->d_in, rgba, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = bu_rgba_encode_blocks_device(ctx, format, map_in ? zin : ctx->d_in, width, height, in_pitch, map_out ? zout : ctx->d_out, 0, ctx->stream);
-    if (st) return st;
-    if (!map_out) BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, need, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
-    return BU_OK;
+    const void* d_rgba = nullptr;
+    void* d_blocks = nullptr;
+    if ((st = call.begin()) || (st = call.output(out, need, need, true, bb, &d_blocks)) || (st = call.input(rgba, in_bytes, true, 4, &d_rgba)) ||
+        (st = bu_rgba_encode_blocks_device(ctx, format, d_rgba, width, height, in_pitch, d_blocks, 0, ctx->stream)))
+        return st;
+    return call.finish();
 }
 
 }  // extern "C"

@@ -145,76 +145,45 @@ static bu_status bu_read_etc1s_streamed(bu_context* ctx, bu_read_target target, 
     bu_status st = bu_etc1s_file_layout(p, l);
     if (st) return leave(st);
 
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> status_words(n_img, 0);  // landing area of the status download: outlives the drain
-    BuDrain drain(ctx);
-    const size_t idx_bytes = (l.words ? l.words : 16) * 4;
-    if (idx_bytes > ctx->h_idx_cap) {
-        if (ctx->h_idx) BU_HIP(ctx, hipHostFree(ctx->h_idx));
-        ctx->h_idx = nullptr;
-        ctx->h_idx_cap = 0;
-        const size_t cap = idx_bytes < ((size_t)4 << 20) ? ((size_t)4 << 20) : idx_bytes + idx_bytes / 4;
-        BU_HIP(ctx, hipHostMalloc(&ctx->h_idx, cap, hipHostMallocDefault));
-        ctx->h_idx_cap = cap;
-    }
+    BuStagedCall call(ctx, n_img);
+    if ((st = call.begin()) || (st = bu_reserve_h_idx(ctx, (l.words ? l.words : 16) * 4))) return st;
     void* d_idx_view = nullptr;
     if (!bu_device_view(ctx->h_idx, &d_idx_view)) return BU_ERR_HIP;
-    void* zout = nullptr;
-    const bool direct_out = bu_device_view(out, &zout);
-    if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
+    void* d_out = nullptr;
     const size_t n_cb = h.total_selectors;
-    const size_t ep_bytes = bu_align256(n_cb * 4), sel_bytes = bu_align256(n_cb * 8), status_bytes = bu_align256(8 * n_img),
-                 desc_bytes = bu_align256(l.descs.size() * sizeof(BuEtc1sSlice));
-    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + 256))) return st;
-    uint8_t* const aux = static_cast<uint8_t*>(ctx->d_aux);
-    uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
-    uint64_t* const d_status = reinterpret_cast<uint64_t*>(aux + ep_bytes + sel_bytes);
-    const BuEtc1sSlice* const d_descs = reinterpret_cast<const BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
-    BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes + sel_bytes + status_bytes, l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
+    // both codebooks, the status words, then one descriptor per image (+ sentinel)
+    enum { EP, SEL, STATUS, DESCS };
+    if ((st = call.output(out, p.out_bytes, p.out_bytes, true, 16, &d_out)) ||
+        (st = call.aux(BuAuxLayout({n_cb * 4, n_cb * 8, 8 * n_img, l.descs.size() * sizeof(BuEtc1sSlice)}), STATUS)) || (st = call.status_reset()))
+        return st;
+    BU_HIP(ctx, hipMemcpyAsync(call.region<void>(DESCS), l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
     lap("reserve");
 
-    // the token buffer of the two-thread slices lives in the context (no memory for it: the ordinary loop)
     const bool may_split = bu_etc1s_may_split(st_tables, lz, !getenv("BU_ETC1S_ONE_THREAD"));
-    const size_t tok_bytes = bu_etc1s_stream_tok_bytes(p, may_split);
-    if (tok_bytes > ctx->lex_cap) {
-        free(ctx->lex_buf);
-        ctx->lex_cap = 0;
-        ctx->lex_buf = malloc(tok_bytes + tok_bytes / 4);
-        if (ctx->lex_buf) ctx->lex_cap = tok_bytes + tok_bytes / 4;
-    }
+    bu_reserve_lex(ctx, bu_etc1s_stream_tok_bytes(p, may_split));
     BuEtc1sSink sink;
     sink.bind = [&]() -> bu_status {
         BU_HIP(ctx, hipSetDevice(ctx->device));
         return BU_OK;
     };
     sink.codebooks = [&](const bu_host::BasisLz& z) -> bu_status {
-        if (!z.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, z.endpoints.data(), z.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (!z.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, z.selectors.data(), z.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (!z.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(call.region<void>(EP), z.endpoints.data(), z.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!z.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(call.region<void>(SEL), z.selectors.data(), z.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
         return BU_OK;
     };
     sink.launch = [&](uint32_t u0, uint32_t u1) -> bu_status {
         const unsigned grid = bu_grid_for((size_t)(u1 - u0) * 64, ctx->cu_count);
-        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_idx_view), d_descs, (uint32_t)(l.descs.size() - 1), u0, u1,
-                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), (uint32_t)n_cb, d_out, d_status);
+        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_idx_view), call.region<const BuEtc1sSlice>(DESCS),
+                             (uint32_t)(l.descs.size() - 1), u0, u1, call.region<const uint32_t>(EP), call.region<const uint2>(SEL), (uint32_t)n_cb,
+                             static_cast<uint8_t*>(d_out), call.d_status);
         BU_HIP(ctx, hipGetLastError());
         return BU_OK;
     };
     BuEtc1sStreamResult res;
     bu_etc1s_stream(file, len, p, l, lz, st_tables, crc_pending, crc_want, static_cast<uint32_t*>(ctx->h_idx), ctx->lex_buf, ctx->lex_cap, may_split, sink, lap, res);
-    if ((st = bu_etc1s_stream_status(crc_pending, st_tables, res))) return st;
-
-    BU_HIP(ctx, hipMemcpyAsync(status_words.data(), d_status, 8 * n_img, hipMemcpyDeviceToHost, ctx->stream));
-    if (p.out_bytes && !direct_out) BU_HIP(ctx, hipMemcpyAsync(out, d_out, p.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
+    if ((st = bu_etc1s_stream_status(crc_pending, st_tables, res)) || (st = call.finish())) return st;
     lap("last band + synchronise");
-    for (size_t k = 0; k < n_img; k++) {
-        st = bu_status_word_decode(status_words[k], nullptr);
-        if (st) return st;
-    }
-    return BU_OK;
+    return call.status(nullptr);
 }
 
 // ---- UASTC file to BU_READ_UASTC: plain copies, no device work (uastc.rs:85-87) ---------------------------------------------------
@@ -252,45 +221,32 @@ static bu_status bu_read_etc1s_one_launch(bu_context* ctx, bu_read_target target
     if (st) return st;
     lap("slice symbol streams");
     const size_t total_in = l.words * 4;
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> words(n_img, 0);  // status landing area: declared before anything is queued, outlives the drain
-    BuDrain drain(ctx);
-    if ((st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, total_in ? total_in : 16))) return st;
-    // a page-locked `out` (bu_host_alloc) receives the kernels' stores directly over PCIe: no device output buffer, no download
-    void* zout = nullptr;
-    const bool direct_out = bu_device_view(out, &zout);
-    if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
-    // behind the codebooks: the status words, then one descriptor per image (+ sentinel)
-    const size_t ep_bytes = bu_align256(lz.endpoints.size() * 4), sel_bytes = bu_align256(lz.selectors.size()), status_bytes = bu_align256(8 * n_img),
-                 desc_bytes = bu_align256(l.descs.size() * sizeof(BuEtc1sSlice));
-    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + status_bytes + desc_bytes + 512))) return st;
-    uint8_t* const d_in = static_cast<uint8_t*>(ctx->d_in);
-    uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
-    uint8_t* const aux = static_cast<uint8_t*>(ctx->d_aux);
-    uint64_t* const d_status = reinterpret_cast<uint64_t*>(aux + ep_bytes + sel_bytes);
-    BuEtc1sSlice* const d_descs = reinterpret_cast<BuEtc1sSlice*>(aux + ep_bytes + sel_bytes + status_bytes);
-    BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(d_in, idx_all.data(), total_in, hipMemcpyHostToDevice, ctx->stream));
-    if (!lz.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(aux, lz.endpoints.data(), lz.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (!lz.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, lz.selectors.data(), lz.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(d_descs, l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
+    BuStagedCall call(ctx, n_img);
+    const void* d_in = nullptr;
+    void* d_out = nullptr;
+    // a page-locked `out` (bu_host_alloc) receives the kernels' stores directly over PCIe: no device output buffer, no download.
+    // Behind the codebooks: the status words, then one descriptor per image (+ sentinel)
+    enum { EP, SEL, STATUS, DESCS };
+    // (d_in is reserved in front of the status reset, the indices go up behind it)
+    if ((st = call.begin()) || (st = call.input(nullptr, total_in, false, 16, nullptr)) || (st = call.output(out, p.out_bytes, p.out_bytes, true, 16, &d_out)) ||
+        (st = call.aux(BuAuxLayout({lz.endpoints.size() * 4, lz.selectors.size(), 8 * n_img, l.descs.size() * sizeof(BuEtc1sSlice)}), STATUS)) ||
+        (st = call.status_reset()) || (st = call.input(idx_all.data(), total_in, false, 16, &d_in)))
+        return st;
+    if (!lz.endpoints.empty()) BU_HIP(ctx, hipMemcpyAsync(call.region<void>(EP), lz.endpoints.data(), lz.endpoints.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!lz.selectors.empty()) BU_HIP(ctx, hipMemcpyAsync(call.region<void>(SEL), lz.selectors.data(), lz.selectors.size(), hipMemcpyHostToDevice, ctx->stream));
+    BU_HIP(ctx, hipMemcpyAsync(call.region<void>(DESCS), l.descs.data(), l.descs.size() * sizeof(BuEtc1sSlice), hipMemcpyHostToDevice, ctx->stream));
     if (l.n_units) {
         const unsigned grid = bu_grid_for((size_t)l.n_units * 64, ctx->cu_count);
-        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, reinterpret_cast<const uint32_t*>(d_in), d_descs, (uint32_t)(l.descs.size() - 1), 0u, l.n_units,
-                             reinterpret_cast<const uint32_t*>(aux), reinterpret_cast<const uint2*>(aux + ep_bytes), (uint32_t)lz.endpoints.size(), d_out, d_status);
+        bu_etc1s_file_launch(ctx, bu_etc1s_file_slot(p, target), grid, static_cast<const uint32_t*>(d_in), call.region<const BuEtc1sSlice>(DESCS),
+                             (uint32_t)(l.descs.size() - 1), 0u, l.n_units, call.region<const uint32_t>(EP), call.region<const uint2>(SEL),
+                             (uint32_t)lz.endpoints.size(), static_cast<uint8_t*>(d_out), call.d_status);
         BU_HIP(ctx, hipGetLastError());
     }
     lap("reserve + enqueue");
     BU_HIP(ctx, hipGetLastError());
-    BU_HIP(ctx, hipMemcpyAsync(words.data(), d_status, 8 * n_img, hipMemcpyDeviceToHost, ctx->stream));
-    if (p.out_bytes && !direct_out) BU_HIP(ctx, hipMemcpyAsync(out, d_out, p.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
+    if ((st = call.finish())) return st;
     lap("download + synchronise");
-    for (size_t k = 0; k < n_img; k++)  // first Err (in slice order) aborts the whole call, like the `?` in the reference drivers
-        if ((st = bu_status_word_decode(words[k], nullptr))) return st;
-    return BU_OK;
+    return call.status(nullptr);
 }
 
 // ---- UASTC file through the kernels -------------------------------------------------------------------------------------------------
@@ -306,25 +262,22 @@ static bu_status bu_read_uastc_runs(bu_context* ctx, bu_read_target target, cons
     const size_t n_img = p.images.size();
     BuUastcFileLayout l;
     bu_uastc_file_layout(p, l);
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> words(n_img, 0);  // status landing area: declared before anything is queued, outlives the drain
     std::vector<BuCrcSeg> crc_segs;         // uploaded file ranges whose 64 KiB pieces the device registers
-    std::vector<uint16_t> crc_parts(crc_deferred ? l.total_in / BU_CRC_PIECE + 1 : 1, 0);  // (landing area too)
+    std::vector<uint16_t> crc_parts(crc_deferred ? l.total_in / BU_CRC_PIECE + 1 : 1, 0);  // landing area of the CRC registers: in front of the call, outlives its drain
     size_t crc_pieces = 0;
-    BuDrain drain(ctx);
+    BuStagedCall call(ctx, n_img);
     bu_status st;
-    if ((st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, l.total_in ? l.total_in : 16))) return st;
+    void* d_out_all = nullptr;
     // a page-locked `out` (bu_host_alloc) receives the kernels' stores directly over PCIe: no device output buffer, no download
-    void* zout = nullptr;
-    const bool direct_out = bu_device_view(out, &zout);
-    if (!direct_out && (st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, p.out_bytes ? p.out_bytes : 16))) return st;
-    const size_t status_bytes = bu_align256(8 * n_img), crc_bytes = bu_align256(2 * crc_parts.size());
-    if ((st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, status_bytes + crc_bytes + 256))) return st;
-    uint8_t* const d_in = static_cast<uint8_t*>(ctx->d_in);
-    uint8_t* const d_out = direct_out ? static_cast<uint8_t*>(zout) : static_cast<uint8_t*>(ctx->d_out);
-    uint64_t* const d_status = static_cast<uint64_t*>(ctx->d_aux);
-    uint16_t* const d_crc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(ctx->d_aux) + status_bytes);
+    enum { STATUS, CRC };
+    if ((st = call.begin()) || (st = call.input(nullptr, l.total_in, false, 16, nullptr)) || (st = call.output(out, p.out_bytes, p.out_bytes, true, 16, &d_out_all)) ||
+        (st = call.aux(BuAuxLayout({8 * n_img, 2 * crc_parts.size()}), STATUS)))
+        return st;
+    const bool direct_out = call.out_mapped;
+    uint8_t* const d_in = static_cast<uint8_t*>(ctx->d_in);  // (only reserved above: the runs go up one by one below)
+    uint8_t* const d_out = static_cast<uint8_t*>(d_out_all);
+    uint64_t* const d_status = call.d_status;
+    uint16_t* const d_crc = call.region<uint16_t>(CRC);
     // registers of the whole 64 KiB pieces of an uploaded range, on the stream that carries its upload
     auto crc_enqueue = [&](const uint8_t* d_range, size_t file_ofs, size_t nbytes, hipStream_t ps) {
         if (!crc_deferred) return;
@@ -333,7 +286,7 @@ static bu_status bu_read_uastc_runs(bu_context* ctx, bu_read_target target, cons
         crc_segs.push_back({file_ofs, nbytes, crc_pieces, np});
         crc_pieces += np;
     };
-    BU_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8 * n_img, ctx->stream));
+    if ((st = call.status_reset())) return st;
     int used_extra = 0;  // own streams 0..used_extra-1 carry pieces (forked behind the status reset, joined on the host)
     const char* const fixed_piece_mib = getenv("BU_RUN_PIECE_MIB");
     const bu_target bt = bu_read_block_target(target);
@@ -382,11 +335,7 @@ static bu_status bu_read_uastc_runs(bu_context* ctx, bu_read_target target, cons
     // HOST -- a cross-stream event wait costs 70-80 us on this runtime, a wait for streams that are nearly done costs nothing
     for (int i = 0; i < used_extra; i++) BU_HIP(ctx, hipStreamSynchronize(ctx->extra_streams[i]));
     BU_HIP(ctx, hipGetLastError());
-    BU_HIP(ctx, hipMemcpyAsync(words.data(), d_status, 8 * n_img, hipMemcpyDeviceToHost, ctx->stream));
-    if (crc_pieces) BU_HIP(ctx, hipMemcpyAsync(crc_parts.data(), d_crc, 2 * crc_pieces, hipMemcpyDeviceToHost, ctx->stream));
-    if (p.out_bytes && !direct_out) BU_HIP(ctx, hipMemcpyAsync(out, d_out, p.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
+    if ((st = call.finish(crc_parts.data(), d_crc, 2 * crc_pieces))) return st;
     lap("download + synchronise");
     if (crc_deferred) {  // the reference checks the CRC before anything else behind the header (basis.rs:338-341): before the status words
         crc_deferred = false;
@@ -394,9 +343,7 @@ static bu_status bu_read_uastc_runs(bu_context* ctx, bu_read_target target, cons
         lap("data CRC fold");
         if (!crc_ok) return BU_ERR_DATA_CRC;
     }
-    for (size_t k = 0; k < n_img; k++)  // first Err (in slice order) aborts the whole call, like the `?` in the reference drivers
-        if ((st = bu_status_word_decode(words[k], nullptr))) return st;
-    return BU_OK;
+    return call.status(nullptr);
 }
 
 // etc1s_six: the call is bu_read_file_to (bu_plan_file)

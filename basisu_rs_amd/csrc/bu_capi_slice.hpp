@@ -157,16 +157,6 @@ bu_status bu_status_word_reset(bu_context* ctx, uint64_t* d_status, void* stream
     return BU_OK;
 }
 
-bu_status bu_status_word_decode(uint64_t word, uint64_t* first_bad_block)
-{
-    if (word == BU_STATUS_WORD_CLEAR) return BU_OK;
-    // a report is (block << 8 | status) with status 1 or 2 (6 for ETC1S; 1 or 17 for the block decoders): anything else was never reset or was overwritten
-    const unsigned st = (unsigned)(word & 0xFFu);
-    if (st != BU_ERR_INVALID_MODE && st != BU_ERR_INVALID_PATTERN && st != BU_ERR_INDEX_RANGE && st != BU_ERR_UNSUPPORTED) return BU_ERR_ARGUMENT;
-    if (first_bad_block) *first_bad_block = word >> 8;
-    return static_cast<bu_status>(st);
-}
-
 bu_status bu_host_alloc(bu_context* ctx, size_t bytes, void** out_ptr)
 {
     if (!ctx || !out_ptr) return BU_ERR_ARGUMENT;
@@ -498,7 +488,7 @@ bu_status bu_uastc_decode_to_rgba(bu_context* ctx, const uint8_t* in, size_t in_
     return bu_uastc_host(ctx, BU_TARGET_RGBA32, in, in_bytes, blocks_per_row, out, out_bytes, first_bad_block);
 }
 
-// ---- launch policy of the slice-level device entry points (include/basisu_hip.h; shapes: bu_context.hpp, BuBigShape) ----
+// ---- launch policy of the slice-level device entry points (include/basisu_hip.h; shapes: bu_launch_plan.hpp, BuBigShape) ----
 bu_status bu_context_set_launch_policy(bu_context* ctx, bu_launch_policy policy)
 {
     if (!ctx || (policy != BU_LAUNCH_EXCLUSIVE && policy != BU_LAUNCH_SHARED && policy != BU_LAUNCH_AUTO)) return BU_ERR_ARGUMENT;
@@ -746,42 +736,30 @@ static bu_status bu_etc1s_host(bu_context* ctx, bu_target target, const uint32_t
     const size_t bb = bu_target_block_bytes(target);
     if (out_bytes < n * bb) return BU_ERR_OUTPUT_SIZE;
     if (n == 0) return BU_OK;
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
-    bu_status st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, n * 4);
-    if (st) return st;
-    st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, n * bb);
-    if (st) return st;
-    const size_t ep_bytes = ((size_t)n_ep * 4 + 15) & ~(size_t)15, sel_bytes = ((size_t)n_sel * 8 + 15) & ~(size_t)15;
-    const size_t a_bytes = alpha_idx ? n * 4 : 0;
-    st = bu_reserve(ctx, &ctx->d_aux, &ctx->aux_cap, ep_bytes + sel_bytes + a_bytes);
-    if (st) return st;
-    uint8_t* aux = static_cast<uint8_t*>(ctx->d_aux);
-    uint64_t word = 0;
-    BuDrain drain(ctx);
-    BU_HIP(ctx, hipMemcpyAsync(ctx->d_in, idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(aux, endpoints, (size_t)n_ep * 4, hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes, selectors, (size_t)n_sel * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (alpha_idx) BU_HIP(ctx, hipMemcpyAsync(aux + ep_bytes + sel_bytes, alpha_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemsetAsync(ctx->d_status, 0xFF, sizeof(uint64_t), ctx->stream));
-    uint64_t* ds = reinterpret_cast<uint64_t*>(ctx->d_status);
-    const uint32_t* d_ep = reinterpret_cast<const uint32_t*>(aux);
-    const void* d_sel = aux + ep_bytes;
-    const uint32_t* d_aidx = alpha_idx ? reinterpret_cast<const uint32_t*>(aux + ep_bytes + sel_bytes) : nullptr;
+    // never mapped: the indices go to d_in, both codebooks and the alpha indices to d_aux (at 16-byte offsets)
+    BuStagedCall call(ctx, 1);
+    bu_status st;
+    const void* d_idx = nullptr;
+    void* d_out = nullptr;
+    if ((st = call.begin()) || (st = call.output(out, n * bb, n * bb, false, 16, &d_out)) ||
+        (st = call.aux(BuAuxLayout({(size_t)n_ep * 4, (size_t)n_sel * 8, alpha_idx ? n * 4 : 0}, 16), -1)) || (st = call.input(idx, n * 4, false, 16, &d_idx)))
+        return st;
+    const uint32_t* d_ep = call.region<uint32_t>(0);
+    const void* d_sel = call.region<void>(1);
+    const uint32_t* d_aidx = alpha_idx ? call.region<uint32_t>(2) : nullptr;
+    BU_HIP(ctx, hipMemcpyAsync(call.region<void>(0), endpoints, (size_t)n_ep * 4, hipMemcpyHostToDevice, ctx->stream));
+    BU_HIP(ctx, hipMemcpyAsync(call.region<void>(1), selectors, (size_t)n_sel * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (alpha_idx) BU_HIP(ctx, hipMemcpyAsync(call.region<void>(2), alpha_idx, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((st = call.status_reset())) return st;
+    uint64_t* ds = call.d_status;
     if (rgba)
-        st = bu_etc1s_decode_rgba_device(ctx, static_cast<const uint32_t*>(ctx->d_in), d_aidx, nbx, nby, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds,
-                                         ctx->stream);
+        st = bu_etc1s_decode_rgba_device(ctx, static_cast<const uint32_t*>(d_idx), d_aidx, nbx, nby, d_ep, n_ep, d_sel, n_sel, d_out, ds, ctx->stream);
     else if (target == BU_TARGET_ETC1)
-        st = bu_etc1s_transcode_etc1_device(ctx, static_cast<const uint32_t*>(ctx->d_in), n, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds, ctx->stream);
+        st = bu_etc1s_transcode_etc1_device(ctx, static_cast<const uint32_t*>(d_idx), n, d_ep, n_ep, d_sel, n_sel, d_out, ds, ctx->stream);
     else
-        st = bu_etc1s_transcode_device(ctx, target, static_cast<const uint32_t*>(ctx->d_in), d_aidx, n, d_ep, n_ep, d_sel, n_sel, ctx->d_out, ds,
-                                       ctx->stream);
-    if (st) return st;
-    BU_HIP(ctx, hipMemcpyAsync(&word, ctx->d_status, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, n * bb, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
-    return bu_status_word_decode(word, first_bad);
+        st = bu_etc1s_transcode_device(ctx, target, static_cast<const uint32_t*>(d_idx), d_aidx, n, d_ep, n_ep, d_sel, n_sel, d_out, ds, ctx->stream);
+    if (st || (st = call.finish())) return st;
+    return call.status(first_bad);
 }
 
 bu_status bu_etc1s_transcode_etc1(bu_context* ctx, const uint32_t* idx, size_t n_blocks, const uint32_t* endpoints, uint32_t n_endpoints,

@@ -1,5 +1,5 @@
-// bu_context (device resources of one context), the error / drain helpers of the host side, the launcher of one slice (bu_launch_uastc:
-// the plan of bu_launch_plan.hpp, launched) and the host-pointer driver shared by the slice-level entry points.
+// bu_context (device resources of one context) and the error / drain / reservation helpers of the host side: everything that needs the HIP
+// runtime API and no kernel (tests/host_emul/bu_staged_call_check.cpp compiles this text for the host against a recording runtime).
 // Part of the single translation unit bu_hip.hip (included there; not a stand-alone header).
 #pragma once
 
@@ -106,83 +106,34 @@ bu_status bu_reserve(bu_context* ctx, void** p, size_t* cap, size_t need)
     return BU_OK;
 }
 
-int bu_auto_policy(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: BU_POLICY_AUTO resolved for one launch on `s`
-void bu_note_big_enqueue(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: a large launch under an explicit policy goes to `s`
-unsigned* bu_ticket_for(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: the tile-ticket pair of an own stream, nullptr for anybody else's
-
-// the kernels a plan names (bu_launch_plan.hpp): BU_TGT_* indexes the plain ones, BU_SORTED_KERNELS[i] is bu_sorted_kernels[i], the multi-run
-// kernel BU_MULTI_* of target T is bu_multi_kernels[T][BU_MULTI_*]
-static_assert(BU_TARGET_ASTC == BU_TGT_ASTC && BU_TARGET_BC7 == BU_TGT_BC7 && BU_TARGET_ETC1 == BU_TGT_ETC1 && BU_TARGET_ETC2 == BU_TGT_ETC2 &&
-              BU_TARGET_RGBA32 == BU_TGT_RGBA && BU_TARGET_BC4_R == BU_TGT_BC4 && BU_TARGET_BC5_RG == BU_TGT_BC5 && BU_TARGET_EAC_R11 == BU_TGT_R11 &&
-                  BU_TARGET_EAC_RG11 == BU_TGT_RG11 && BU_TARGET_BC1_RGB == BU_TGT_BC1 && BU_TARGET_BC3_RGBA == BU_TGT_BC3,
-              "the launchers index kernels by bu_target");
-constexpr unsigned BU_N_TARGETS = BU_TGT_BC3 + 1;  // (entries 5 and 10 of the tables are empty: they name no target, bu_target_block_bytes() == 0)
-using BuPlainFn = decltype(&bu_uastc_kernel<BU_TGT_ASTC>);
-const BuPlainFn bu_plain_kernels[BU_N_TARGETS] = {bu_uastc_kernel<BU_TGT_ASTC>, bu_uastc_kernel<BU_TGT_BC7>, bu_uastc_kernel<BU_TGT_ETC1>, bu_uastc_kernel<BU_TGT_ETC2>,
-                                                  bu_uastc_kernel<BU_TGT_RGBA>, nullptr, bu_uastc_kernel<BU_TGT_BC4>, bu_uastc_kernel<BU_TGT_BC5>, bu_uastc_kernel<BU_TGT_R11>,
-                                                  bu_uastc_kernel<BU_TGT_RG11>, nullptr, bu_uastc_kernel<BU_TGT_BC1>, bu_uastc_kernel<BU_TGT_BC3>};
-using BuSortedFn = decltype(&bu_uastc_sorted_kernel<BU_TGT_BC7, 1024, 1, 1, false, BU_LAYOUT_STRIP>);
-template <size_t... I>
-constexpr std::array<BuSortedFn, sizeof...(I)> bu_sorted_fns(std::index_sequence<I...>)
+// the page-locked index buffer of the streamed ETC1S front door (h_idx), of at least `bytes`
+bu_status bu_reserve_h_idx(bu_context* ctx, size_t idx_bytes)
 {
-    constexpr const BuSortedKey* K = BU_SORTED_KERNELS;
-    return {bu_uastc_sorted_kernel<K[I].target, K[I].wgs, K[I].bpt, K[I].minw, K[I].prefetch, K[I].rect ? BU_LAYOUT_RECT : BU_LAYOUT_STRIP>...};
-}
-const std::array<BuSortedFn, std::size(BU_SORTED_KERNELS)> bu_sorted_kernels = bu_sorted_fns(std::make_index_sequence<std::size(BU_SORTED_KERNELS)>());
-using BuMultiFn = decltype(&bu_uastc_multi_kernel<BU_TGT_BC7, 1024, 1>);
-template <int T>
-std::array<BuMultiFn, 4> bu_multi_fns()  // indexed by BU_MULTI_*; nullptr where T has no such kernel
-{
-    BuMultiFn etc_2048 = nullptr, whole = nullptr;
-    if constexpr (bu_etc_family(T)) etc_2048 = bu_uastc_multi_kernel<T, 512, 4>;
-    if constexpr (T == BU_TGT_BC7 || T == BU_TGT_ASTC) whole = bu_uastc_multi_kernel<T, 256, 4, true, true>;
-    return {etc_2048, bu_uastc_multi_kernel<T, 1024, 1>, whole, bu_uastc_multi_kernel<T, 512, 2, true>};
-}
-const std::array<BuMultiFn, 4> bu_multi_kernels[BU_N_TARGETS] = {bu_multi_fns<BU_TGT_ASTC>(), bu_multi_fns<BU_TGT_BC7>(), bu_multi_fns<BU_TGT_ETC1>(),
-                                                                 bu_multi_fns<BU_TGT_ETC2>(), bu_multi_fns<BU_TGT_RGBA>(), {}, bu_multi_fns<BU_TGT_BC4>(),
-                                                                 bu_multi_fns<BU_TGT_BC5>(), bu_multi_fns<BU_TGT_R11>(), bu_multi_fns<BU_TGT_RG11>(), {},
-                                                                 bu_multi_fns<BU_TGT_BC1>(), bu_multi_fns<BU_TGT_BC3>()};
-
-// the rectangle kernels (bu_uastc_transcode_rects_device): one per target
-using BuRectsFn = decltype(&bu_uastc_rects_kernel<BU_TGT_BC7>);
-const BuRectsFn bu_rects_kernels[BU_N_TARGETS] = {bu_uastc_rects_kernel<BU_TGT_ASTC>, bu_uastc_rects_kernel<BU_TGT_BC7>, bu_uastc_rects_kernel<BU_TGT_ETC1>,
-                                                  bu_uastc_rects_kernel<BU_TGT_ETC2>, bu_uastc_rects_kernel<BU_TGT_RGBA>, nullptr, bu_uastc_rects_kernel<BU_TGT_BC4>,
-                                                  bu_uastc_rects_kernel<BU_TGT_BC5>, bu_uastc_rects_kernel<BU_TGT_R11>, bu_uastc_rects_kernel<BU_TGT_RG11>, nullptr,
-                                                  bu_uastc_rects_kernel<BU_TGT_BC1>, bu_uastc_rects_kernel<BU_TGT_BC3>};
-
-// One slice: resolve the policy, plan (bu_plan_slice), claim tile tickets where the plan asks for them, launch.
-// policy = BU_POLICY_* of this launch, or -1 for the context's (bu_context_set_launch_policy; BU_POLICY_AUTO there is resolved per launch by
-// bu_auto_policy): only the device-pointer slice entry points pass -1 -- the host-pointer and whole-file entry points issue their launches one
-// after another on one stream, for which the exclusive shapes are the right ones whatever the context says.
-bu_status bu_launch_uastc(bu_context* ctx, bu_target target, const void* d_in, size_t n_blocks, void* d_out, size_t bpr,
-                          uint64_t base, uint64_t* d_status, hipStream_t stream, unsigned grid_cap = 0, int policy = BU_POLICY_EXCLUSIVE)
-{
-    if (n_blocks == 0) return BU_OK;
-    if (bu_target_block_bytes(target) == 0) return BU_ERR_ARGUMENT;  // (also the empty entries 5 and 10 of the kernel tables)
-    const unsigned cu_count = (unsigned)ctx->cu_count;
-    if (policy < 0) policy = ctx->launch_policy.load(std::memory_order_relaxed);
-    const bool big = bu_slice_needs_policy(n_blocks, grid_cap, cu_count);
-    if (policy == BU_POLICY_AUTO) policy = big ? bu_auto_policy(ctx, stream) : (int)BU_POLICY_EXCLUSIVE;
-    else if (big) bu_note_big_enqueue(ctx, stream);
-    std::vector<BuSliceLaunch> plan;
-    bu_plan_slice(target, n_blocks, bpr, grid_cap, policy, cu_count, plan);
-    const uint4* in = static_cast<const uint4*>(d_in);
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(d_status);
-    const size_t obytes = bu_target_block_bytes(target);
-    for (const BuSliceLaunch& l : plan) {
-        void* out = static_cast<uint8_t*>(d_out) + l.offset * obytes;  // RGBA32: the plan cuts on whole rows
-        if (l.kernel < 0) {
-            hipLaunchKernelGGL(bu_plain_kernels[target], dim3(l.grid), dim3(l.block), 0, stream, in + l.offset, out, l.n, (unsigned)l.bpr, base + l.offset, st,
-                               ctx->d_tables);
-        } else {
-            unsigned* const ticket = l.wants_ticket ? bu_ticket_for(ctx, stream) : nullptr;
-            hipLaunchKernelGGL(bu_sorted_kernels[l.kernel], dim3(l.grid), dim3(l.block), 0, stream, in + l.offset, out, (unsigned)l.n, (unsigned)l.bpr,
-                               (unsigned long long)(base + l.offset), st, ctx->d_tables, l.cus, BU_SORTED_KERNELS[l.kernel].rect ? l.rect_magic : l.tile_rt, ticket);
-        }
-        BU_HIP(ctx, hipGetLastError());
+    if (idx_bytes > ctx->h_idx_cap) {
+        if (ctx->h_idx) BU_HIP(ctx, hipHostFree(ctx->h_idx));
+        ctx->h_idx = nullptr;
+        ctx->h_idx_cap = 0;
+        const size_t cap = idx_bytes < ((size_t)4 << 20) ? ((size_t)4 << 20) : idx_bytes + idx_bytes / 4;
+        BU_HIP(ctx, hipHostMalloc(&ctx->h_idx, cap, hipHostMallocDefault));
+        ctx->h_idx_cap = cap;
     }
     return BU_OK;
 }
+
+// the token buffer of the two-thread slices lives in the context (no memory for it: lex_cap stays 0, the ordinary loop)
+void bu_reserve_lex(bu_context* ctx, size_t tok_bytes)
+{
+    if (tok_bytes > ctx->lex_cap) {
+        free(ctx->lex_buf);
+        ctx->lex_cap = 0;
+        ctx->lex_buf = malloc(tok_bytes + tok_bytes / 4);
+        if (ctx->lex_buf) ctx->lex_cap = tok_bytes + tok_bytes / 4;
+    }
+}
+
+int bu_auto_policy(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: BU_POLICY_AUTO resolved for one launch on `s`
+void bu_note_big_enqueue(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: a large launch under an explicit policy goes to `s`
+unsigned* bu_ticket_for(bu_context* ctx, hipStream_t s);  // bu_streams.hpp: the tile-ticket pair of an own stream, nullptr for anybody else's
 
 // device-side address of a page-locked host buffer; false for ordinary (pageable) memory
 bool bu_device_view(const void* p, void** dev)
@@ -196,80 +147,6 @@ bool bu_device_view(const void* p, void** dev)
     if (reinterpret_cast<uintptr_t>(a.devicePointer) % 16 != 0) return false;  // the kernels move 16-byte vectors
     *dev = a.devicePointer;
     return true;
-}
-
-// host-pointer UASTC driver shared by transcode / decode_to_rgba / the per-block API
-bu_status bu_uastc_host(bu_context* ctx, bu_target target, const uint8_t* in, size_t in_bytes, size_t bpr, uint8_t* out,
-                        size_t out_bytes, uint64_t* first_bad)
-{
-    if (!ctx || (!in && in_bytes) || !out) return BU_ERR_ARGUMENT;
-    const size_t bb = bu_target_block_bytes(target);
-    if (bb == 0) return BU_ERR_ARGUMENT;
-    if (in_bytes % 16 != 0) return BU_ERR_LENGTH;  // uastc.rs:54-59
-    const size_t n = in_bytes / 16;
-    if (out_bytes < n * bb) return BU_ERR_OUTPUT_SIZE;
-    if (target == BU_TARGET_RGBA32 && bpr == 0) return BU_ERR_ARGUMENT;
-    if (n == 0) return BU_OK;
-    std::lock_guard<std::mutex> g(ctx->lock);
-    BU_HIP(ctx, hipSetDevice(ctx->device));
-    bu_status st;
-    // Page-locked caller buffers (bu_host_alloc, or anything the caller page-locked with the HIP runtime) are visible to
-    // the GPU: the kernels read the slice and / or write the result straight over PCIe -- no staging copy on that side.
-    // A small persistent grid walks the tiles with prefetch, so tile k's posted writes travel upstream while tile k+1's
-    // reads come down (PCIe is full duplex): 0.45 ms per 4096^2 atlas with both sides mapped, against 0.69 ms for upload +
-    // kernel + download.  Ordinary pageable memory cannot be mapped and is staged through the context's device buffers.
-    void *zin = nullptr, *zout = nullptr;
-    const bool map_in = bu_device_view(in, &zin);
-    // RGBA32 with a ragged last block row stores whole image rows, past the 64*n bytes the caller sized: keep that staged
-    const bool map_out = !(target == BU_TARGET_RGBA32 && n % bpr != 0) && bu_device_view(out, &zout);
-    if (!map_in) {
-        st = bu_reserve(ctx, &ctx->d_in, &ctx->in_cap, in_bytes);
-        if (st) return st;
-    }
-    if (!map_out) {
-        size_t out_need = n * bb;
-        if (target == BU_TARGET_RGBA32) out_need = ((n + bpr - 1) / bpr) * bpr * 64;
-        st = bu_reserve(ctx, &ctx->d_out, &ctx->out_cap, out_need);
-        if (st) return st;
-    }
-    const void* din = map_in ? zin : ctx->d_in;
-    void* dout = map_out ? zout : ctx->d_out;
-    uint64_t word = 0;
-    BuDrain drain(ctx);
-    if (!map_in) BU_HIP(ctx, hipMemcpyAsync(ctx->d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BU_HIP(ctx, hipMemsetAsync(ctx->d_status, 0xFF, sizeof(uint64_t), ctx->stream));
-    st = bu_launch_uastc(ctx, target, din, n, dout, bpr, 0, reinterpret_cast<uint64_t*>(ctx->d_status), ctx->stream,
-                         (map_in || map_out) ? BU_ZEROCOPY_GRID : 0);
-    if (st) return st;
-    BU_HIP(ctx, hipMemcpyAsync(&word, ctx->d_status, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    if (!map_out) BU_HIP(ctx, hipMemcpyAsync(out, ctx->d_out, n * bb, hipMemcpyDeviceToHost, ctx->stream));
-    BU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
-    return bu_status_word_decode(word, first_bad);
-}
-
-// ---- the per-block API's host side (bu_capi_slice.hpp): the product's block code compiled for the host, over a host copy of the tables
-const BuTablesAll& bu_host_tables()
-{
-    static const BuTablesAll* const tables = [] {
-        BuTablesAll* t = new BuTablesAll();
-        bu_build_tables(t);
-        return t;
-    }();
-    return *tables;
-}
-
-template <int TARGET>
-bu_status bu_block_on_host(const uint8_t in[16], void* out)
-{
-    const BuTables& T = bu_host_tables().t;
-    BuBlk b;
-    memcpy(b.w, in, 16);
-    constexpr int NO = TARGET == BU_TGT_RGBA ? 16 : (TARGET == BU_TGT_ETC1 ? 2 : 4);
-    uint32_t o[16] = {0};  // a failing block leaves its zeros (every path checks before it writes), as the kernels' result slots do
-    const int st = bu_block_any<TARGET>(T, T.mode_lut[b.w[0] & 127u], b, o);
-    memcpy(out, o, NO * sizeof(uint32_t));
-    return st == BU_ST_OK ? BU_OK : (st == BU_ST_BAD_PATTERN ? BU_ERR_INVALID_PATTERN : BU_ERR_INVALID_MODE);
 }
 
 }  // namespace

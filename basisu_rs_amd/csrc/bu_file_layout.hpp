@@ -1,8 +1,10 @@
 // Host-side layout of the whole-file calls (bu_capi_file.hpp): where the slices of a planned file (BuFilePlan, bu_container.hpp) go in the staged input, what the
-// whole-file ETC1S kernels are told about them, how a UASTC run is cut into pieces, and the fold of the device's CRC piece registers.  Pure arithmetic
+// whole-file ETC1S kernels are told about them, how a UASTC run is cut into pieces, how the aux buffer of a blocking host-pointer call is carved
+// into regions (BuAuxLayout), and the fold of the device's CRC piece registers.  Pure arithmetic
 // over file fields -- the code that faces a hostile slice table.  No HIP in here: tests/host_emul/bu_emul_file_layout.cpp compiles it as it is and
 // tests/test_file_layout.py checks it without a GPU.
 #pragma once
+#include <assert.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -95,6 +97,38 @@ struct BuUastcFileLayout {
 };
 
 inline size_t bu_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- the carve-up of the context's aux buffer -------------------------------------------------------------------------------------------
+// The blocking host-pointer calls (bu_staged_call.hpp) keep what is neither input nor output in ONE device buffer: codebooks, status words,
+// slice table, CRC registers.  From the byte sizes of the regions a call wants, in order: where each starts -- a multiple of `align`, a power
+// of two -- and what to reserve, the rounded sizes and BU_AUX_SLACK.
+constexpr size_t BU_AUX_SLACK = 512;
+constexpr size_t BU_AUX_MAX_REGIONS = 4;
+struct BuAuxLayout {
+    size_t n = 0, off[BU_AUX_MAX_REGIONS] = {}, total = BU_AUX_SLACK;
+    BuAuxLayout() = default;
+    BuAuxLayout(const size_t* sizes, size_t n_sizes, size_t align = 256) : n(n_sizes)
+    {
+        assert(n_sizes <= BU_AUX_MAX_REGIONS && align && (align & (align - 1)) == 0);
+        size_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            off[i] = at;
+            at += (sizes[i] + align - 1) & ~(align - 1);
+        }
+        total = at + BU_AUX_SLACK;
+    }
+    // BuAuxLayout({a, b, c}) / BuAuxLayout({a, b, c}, 16): one region more than the layout holds does not compile
+    template <size_t N>
+    BuAuxLayout(const size_t (&sizes)[N], size_t align = 256) : BuAuxLayout(sizes, N, align)
+    {
+        static_assert(N <= BU_AUX_MAX_REGIONS, "BuAuxLayout holds BU_AUX_MAX_REGIONS regions");
+    }
+    size_t at(size_t i) const
+    {
+        assert(i < n);
+        return off[i];
+    }
+};
 
 // a slice joins its predecessor's run when it starts where that one ends and both are whole blocks, at least one
 inline void bu_uastc_file_layout(const bu_host::BuFilePlan& p, BuUastcFileLayout& l)

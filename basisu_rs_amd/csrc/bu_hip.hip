@@ -49,7 +49,9 @@
 #include "bu_etc1s_kernels.hpp"  // device code: the ETC1S back end
 #include "bu_decode_kernels.hpp" // device code: blocks -> RGBA8 image
 #include "bu_encode_kernels.hpp" // device code: RGBA8 image -> blocks
-#include "bu_context.hpp"        // bu_context, launcher, host-pointer driver
+#include "bu_context.hpp"        // bu_context, error / drain / reservation helpers (HIP runtime API only, no kernel)
+#include "bu_staged_call.hpp"    // the protocol of the blocking host-pointer entry points (HIP runtime API only, no kernel)
+#include "bu_uastc_launch.hpp"   // kernel tables, launcher of one UASTC slice, host-pointer UASTC driver
 #include "bu_streams.hpp"        // the context's own streams (hardware-queue check), BU_LAUNCH_AUTO
 #include "bu_capi_slice.hpp"     // extern "C": slice level
 #include "bu_capi_file.hpp"      // extern "C": whole-file level

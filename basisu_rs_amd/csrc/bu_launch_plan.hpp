@@ -1,4 +1,4 @@
-// The launch plan of the UASTC launchers (bu_context.hpp bu_launch_uastc: one slice; bu_capi_slice.hpp bu_launch_runs: several runs): which
+// The launch plan of the UASTC launchers (bu_uastc_launch.hpp bu_launch_uastc: one slice; bu_capi_slice.hpp bu_launch_runs: several runs): which
 // instantiation of the mode-sorted kernel runs, on which grid, with which tile size, priorities, pitch and tile tickets.  No HIP in here: the
 // test-only host build (tests/host_emul) compiles it as it is and tests/test_launch_plan.py checks it case by case without a GPU.
 #pragma once
@@ -109,7 +109,7 @@ constexpr BuShape BuEtcMidShape{512, 2, 1, false, false, 3};
 constexpr BuShape BuZeroCopyShape{256, 4, 1, true, false, 1};
 constexpr int BU_HOST_TILE = 1024;  // the tile the launcher counts in where the shape does not say otherwise
 
-// The compiled instantiations of bu_uastc_sorted_kernel<target, WGS, BPT, MINW, PREFETCH, RECT ? layout RECT : STRIP> (bu_context.hpp launches entry i):
+// The compiled instantiations of bu_uastc_sorted_kernel<target, WGS, BPT, MINW, PREFETCH, RECT ? layout RECT : STRIP> (bu_uastc_launch.hpp launches entry i):
 // every shape above in the strip layout, and in the rectangular one where it has RECT.  (Never planned, compiled all the same: the ETC mid shape for BC7 /
 // ASTC, the 256 x 4 RECT shape for ETC1 / ETC2.)
 struct BuSortedKey { int target, wgs, bpt, minw; bool prefetch, rect; };

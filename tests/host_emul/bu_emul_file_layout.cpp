@@ -4,6 +4,7 @@
 //   etc1s-huge                                  the same for a hand-made plan of two slices of 65 535 x 65 535 blocks (no file bytes)
 //   runs <read target> <file>                   the UASTC runs
 //   piece <run bytes> <read target> <mapped: 0 | 1> [<BU_RUN_PIECE_MIB>]
+//   aux <alignment> <region bytes> ...          the carve-up of the aux buffer (BuAuxLayout): offset of every region, total with the slack
 //   fold <file> <offset:length> ...             the payload CRC folded from piece registers of those ranges (crc16_raw from a zero register,
 //                                               what bu_crc16_pieces_kernel leaves) against the header's data_crc16
 #include <stdio.h>
@@ -94,6 +95,15 @@ int main(int argc, char** argv)
     if (cmd == "piece" && (argc == 5 || argc == 6)) {
         const size_t run_bytes = strtoull(argv[2], nullptr, 10), piece = bu_run_piece_bytes(run_bytes, argc == 6 ? argv[5] : nullptr);
         printf("{\"piece\": %zu, \"pieced\": %d}\n", piece, (int)bu_run_is_pieced((bu_read_target)atoi(argv[3]), atoi(argv[4]) != 0, piece, run_bytes));
+        return 0;
+    }
+    if (cmd == "aux" && argc >= 3 && (size_t)argc - 3 <= BU_AUX_MAX_REGIONS) {
+        std::vector<size_t> sizes;
+        for (int a = 3; a < argc; a++) sizes.push_back(strtoull(argv[a], nullptr, 10));
+        const BuAuxLayout l(sizes.data(), sizes.size(), strtoull(argv[2], nullptr, 10));
+        printf("{\"slack\": %zu, \"total\": %zu, ", BU_AUX_SLACK, l.total);
+        list("off", std::vector<size_t>(l.off, l.off + l.n), num, "");
+        printf("}\n");
         return 0;
     }
     if (cmd == "fold" && argc >= 3) {

@@ -1,6 +1,6 @@
 """The whole-file layout (csrc/bu_file_layout.hpp) on the CPU, through the stand-alone host build tests/host_emul/bu_emul_file_layout.cpp compiled with and
-without -fsanitize=undefined (a report aborts it): the ETC1S index buffer and slice table against a model written here, the UASTC runs and the piece sizes
-against literals, the fold of the CRC piece registers against the plain CRC."""
+without -fsanitize=undefined (a report aborts it): the ETC1S index buffer and slice table against a model written here, the UASTC runs, the piece sizes
+and the carve-up of the aux buffer against literals, the fold of the CRC piece registers against the plain CRC."""
 import json
 import os
 import subprocess
@@ -187,6 +187,47 @@ def test_fixed_piece_size(layout):
         assert layout("piece", run, _lib.READ_ETC2, 1, 0) == dict(piece=0, pieced=0)
         assert layout("piece", run, _lib.READ_ETC2, 1, 1) == dict(piece=MIB, pieced=int(run >= 2 * MIB))
         assert layout("piece", run, _lib.READ_RGBA, 1, 1)["pieced"] == 0 and layout("piece", run, _lib.READ_ETC2, 0, 1)["pieced"] == 0
+
+
+# ---- the aux buffer ---------------------------------------------------------------------------------------------------------------------
+AUX_SLACK = 512
+
+
+@pytest.mark.parametrize("align", [16, 256])
+@pytest.mark.parametrize("sizes", [[1], [255, 256, 257], [4000, 8000, 24, 128], [0, 0, 0, 0], [7, 0, 9], [0, 100], [100, 0], [1 << 33, 3, 1 << 20, 17], []],
+                         ids=lambda s: "-".join(map(str, s)) or "none")
+def test_aux_regions_are_aligned_ordered_and_disjoint(layout, sizes, align):
+    got = layout("aux", align, *sizes)
+    off = got["off"]
+    assert got["slack"] == AUX_SLACK and len(off) == len(sizes)
+    assert all(o % align == 0 for o in off) and (not off or off[0] == 0)
+    rounded = [(s + align - 1) // align * align for s in sizes]
+    for i in range(1, len(off)):
+        # ordered, and a region ends where the next begins or before: strictly ordered wherever the region in front holds a byte
+        assert off[i] >= off[i - 1] + sizes[i - 1] and (off[i] > off[i - 1] or sizes[i - 1] == 0)
+        assert off[i] == off[i - 1] + rounded[i - 1]
+    assert got["total"] == sum(rounded) + AUX_SLACK
+    assert not off or off[-1] + sizes[-1] <= got["total"] - AUX_SLACK
+
+
+# what the four drivers ask for, against the sums they used to write out inline (a + b: bu_align256(a) + bu_align256(b), as plain numbers)
+AUX_SHAPES = {
+    # 1000 codebook entries, 3 images, 4 descriptors of 32 bytes: 4 n, 8 n, 8 per image, the table
+    "streamed ETC1S": (256, [4000, 8000, 24, 128], [0, 4096, 4096 + 8192, 4096 + 8192 + 256], 4096 + 8192 + 256 + 256),
+    # 300 endpoints of 4 bytes, 300 selectors of 8, 40 images, 41 descriptors
+    "one-launch ETC1S": (256, [1200, 2400, 320, 1312], [0, 1280, 1280 + 2560, 1280 + 2560 + 512], 1280 + 2560 + 512 + 1536),
+    # 47 images, 257 CRC registers of 2 bytes
+    "UASTC runs": (256, [376, 514], [0, 512], 512 + 768),
+    # the slice-level ETC1S calls round to 16: 37 endpoints, 21 selectors, 65 alpha indices -- or none
+    "ETC1S slice with alpha": (16, [148, 168, 260], [0, 160, 160 + 176], 160 + 176 + 272),
+    "ETC1S slice": (16, [148, 168, 0], [0, 160, 160 + 176], 160 + 176),
+}
+
+
+@pytest.mark.parametrize("name", list(AUX_SHAPES))
+def test_aux_offsets_of_the_drivers_are_the_inline_sums(layout, name):
+    align, sizes, off, regions = AUX_SHAPES[name]
+    assert layout("aux", align, *sizes) == dict(slack=AUX_SLACK, off=off, total=regions + AUX_SLACK)
 
 
 # ---- the CRC fold -----------------------------------------------------------------------------------------------------------------------
