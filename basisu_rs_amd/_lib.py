@@ -26,6 +26,7 @@ SYMBOLS = [
     "bu_etc1s_selector_from_rows", "bu_etc1s_transcode_etc1_device", "bu_etc1s_decode_rgba_device",
     "bu_etc1s_transcode_etc1", "bu_etc1s_decode_rgba", "bu_etc1s_transcode_device", "bu_etc1s_transcode", "bu_etc1s_transcode_rects_device",
     "bu_blocks_decode_rgba_device", "bu_blocks_decode_rgba", "bu_rgba_encode_blocks_device", "bu_rgba_encode_blocks",
+    "bu_rgba_encode_uastc_device", "bu_rgba_encode_uastc",
     "bu_basis_read_header", "bu_basis_read_slice_descs", "bu_basis_crc16", "bu_read_query", "bu_read_to", "bu_read_file_query", "bu_read_file_to", "bu_basislz_decode",
     "bu_basis_write_uastc",
     "bu_comm_unique_id", "bu_comm_create", "bu_comm_destroy", "bu_comm_query", "bu_allgather_inplace",
@@ -172,6 +173,11 @@ def load():
         lib.bu_rgba_encode_blocks_device.restype = c.c_int
         lib.bu_rgba_encode_blocks.argtypes = [vp, c.c_int, vp, sz, sz, sz, vp, sz]
         lib.bu_rgba_encode_blocks.restype = c.c_int
+    if hasattr(lib, "bu_rgba_encode_uastc_device"):  # (the same)
+        lib.bu_rgba_encode_uastc_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp]
+        lib.bu_rgba_encode_uastc_device.restype = c.c_int
+        lib.bu_rgba_encode_uastc.argtypes = [vp, vp, sz, sz, sz, vp, sz]
+        lib.bu_rgba_encode_uastc.restype = c.c_int
     szp = c.POINTER(sz)
     lib.bu_basis_read_header.argtypes = [vp, sz, c.POINTER(BasisHeader)]
     lib.bu_basis_read_header.restype = c.c_int

@@ -163,6 +163,21 @@ class Context:
         self._check(st)
         return out[: n * bb]
 
+    def encode_uastc(self, rgba, width, height, in_pitch=0, out=None):
+        """bu_rgba_encode_uastc: an RGBA8 image of width x height pixels, pixel rows in_pitch bytes apart (0 = 4 * width), -> UASTC blocks, ceil(width / 4)
+        per row, tight: the input of every transcode here and of write_uastc_file.  Partial edge blocks repeat the last column
+        and row.  `rgba` holds (height - 1) * in_pitch + 4 * width bytes at least."""
+        a = _as_u8(rgba)
+        w, h, pitch = int(width), int(height), int(in_pitch)
+        if w > 0 and h > 0 and a.size < (h - 1) * (pitch or 4 * w) + 4 * w:
+            raise ValueError("rgba holds fewer bytes than the image")
+        n = ((w + 3) // 4) * ((h + 3) // 4)
+        if out is None:
+            out = np.empty(max(n, 1) * 16, dtype=np.uint8)
+        st = self._lib.bu_rgba_encode_uastc(self._h, a.ctypes.data, w, h, pitch, out.ctypes.data, out.size)
+        self._check(st)
+        return out[: n * 16]
+
     def set_launch_policy(self, shared):
         """bu_context_set_launch_policy.  "auto" / None (the default of a new context) = BU_LAUNCH_AUTO: decided per call -- shared when the launch goes
         to one of the context's own streams and another of them has work in flight, exclusive otherwise; False = BU_LAUNCH_EXCLUSIVE: a large launch
@@ -299,6 +314,13 @@ class Context:
         4 * width bytes; out_pitch = 0: block rows of ceil(width / 4) blocks, tight.  No block can fail, so there is no status word."""
         st = self._lib.bu_rgba_encode_blocks_device(self._h, int(fmt), _ptr(d_rgba), int(width), int(height), int(in_pitch), _ptr(d_blocks), int(out_pitch),
                                                     _stream_ptr(stream))
+        self._check(st)
+
+    def encode_uastc_device(self, d_rgba, width, height, d_blocks, in_pitch=0, out_pitch=0, stream=None):
+        """bu_rgba_encode_uastc_device: the device form of encode_uastc (torch tensors or raw pointers); only enqueues.  in_pitch = 0: pixel rows of
+        4 * width bytes; out_pitch = 0: block rows of ceil(width / 4) blocks, tight.  No block can fail, so there is no status word."""
+        st = self._lib.bu_rgba_encode_uastc_device(self._h, _ptr(d_rgba), int(width), int(height), int(in_pitch), _ptr(d_blocks), int(out_pitch),
+                                                   _stream_ptr(stream))
         self._check(st)
 
     def transcode_device_sync(self, fmt, d_in, n_blocks, d_out, blocks_per_row=0, block_index_base=0):

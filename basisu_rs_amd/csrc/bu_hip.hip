@@ -38,6 +38,7 @@
 #include "bu_etc1s_targets.hpp"   // ETC1S per block: index check, ETC1, RGBA32, BC1 / BC3 / BC4 / BC5 / EAC R11 / RG11 (palette form)
 #include "bu_decode_blocks.hpp"   // block decoders: the ten block formats -> 16 RGBA8 texels
 #include "bu_encode_blocks.hpp"   // block encoders from pixels: 16 RGBA8 texels -> BC4 / BC5 / EAC R11 / RG11 / BC1 / BC3, and the gather of a block's texels
+#include "bu_uastc_encode.hpp"    // the UASTC encoder from pixels: 16 RGBA8 texels -> one UASTC block
 #include "bu_launch_plan.hpp"  // kernel, grid and arguments of every UASTC launch (host only)
 #include "bu_rect_plan.hpp"    // rectangles of slices into pitched surfaces: job table, address mapping, launch plan
 #include "bu_etc1s_rect_plan.hpp"  // the same for ETC1S slices: 64-block units, a wave each
@@ -49,6 +50,7 @@
 #include "bu_etc1s_kernels.hpp"  // device code: the ETC1S back end
 #include "bu_decode_kernels.hpp" // device code: blocks -> RGBA8 image
 #include "bu_encode_kernels.hpp" // device code: RGBA8 image -> blocks
+#include "bu_uastc_encode_kernels.hpp" // device code: RGBA8 image -> UASTC blocks
 #include "bu_context.hpp"        // bu_context, error / drain / reservation helpers (HIP runtime API only, no kernel)
 #include "bu_staged_call.hpp"    // the protocol of the blocking host-pointer entry points (HIP runtime API only, no kernel)
 #include "bu_uastc_launch.hpp"   // kernel tables, launcher of one UASTC slice, host-pointer UASTC driver
@@ -58,4 +60,4 @@
 #include "bu_capi_measure.hpp"   // extern "C": measurement helpers
 #include "bu_multi.hpp"          // extern "C": multi-GPU
 #include "bu_capi_decode.hpp"    // extern "C": blocks of the ten block formats -> RGBA8
-#include "bu_capi_encode.hpp"    // extern "C": an RGBA8 image -> blocks of the six formats with an encoder from texels
+#include "bu_capi_encode.hpp"    // extern "C": an RGBA8 image -> blocks of the six formats with an encoder from texels, and -> UASTC blocks

@@ -46,6 +46,8 @@ BU_DEV void bu_eac_solid(uint32_t out[2], uint32_t value)
 // PAL = 0: every texel goes through the threshold count.  PAL = 4 / 8: the block's alphas come from a palette of that many
 // byte entries (the 2-bit-weight modes, bu_block_unpack): the count runs over the palette, and a texel column picks its
 // indices up with the same v_perm selector `asel[x]` that interpolated its alpha.
+// (bu_enc_etc2tm of bu_uastc_encode.hpp restates the centre, the values and the thresholds below to search etc2tm for the block this function will
+// write: a change of the rule here has to be made there too.  tests/test_uastc_encode.py compares the two through the oracle's ETC2 transcode.)
 template <int PAL>
 BU_DEV void bu_eac_block(const BuTables& T, uint32_t out[2], uint32_t etc2tm, const uint32_t px[16], const uint32_t apal[2], const uint32_t asel[4])
 {

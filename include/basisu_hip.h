@@ -433,6 +433,23 @@ bu_status bu_rgba_encode_blocks_device(bu_context* ctx, bu_target format, const 
 bu_status bu_rgba_encode_blocks(bu_context* ctx, bu_target format, const uint8_t* rgba, size_t width, size_t height,
                                 size_t in_pitch_bytes, uint8_t* out, size_t out_bytes);
 
+/* ---- pixels -> UASTC: the encoder that makes the library's own input --------
+ * An RGBA8 image -> UASTC blocks.  Geometry, alignment (d_rgba to 4, d_blocks to 16), pitch rules, edge replication, the empty-image rule, what is
+ * read and written, the BU_ERR_ARGUMENT cases (but for the format, which this call does not take) and BU_ERR_OUTPUT_SIZE are those of
+ * bu_rgba_encode_blocks_device / bu_rgba_encode_blocks above with a block size of 16 bytes; nothing is launched on a refusal.
+ *   Blocks: every block is a valid UASTC block of a single-subset, single-plane mode -- 8 for 16 equal texels; the best of 5, 0, 18 where every
+ *   A == 255; 15 where R == G == B in every texel; else the best of 14, 12, 10 -- chosen and fitted by the exact integer rule of section 4.11
+ *   (the bytes are those of the numpy model tests/uastc_encode_model.py).  Hints: etc2tm of the alpha modes, mode 8's ETC1 fields and the ETC1 flip /
+ *   diff / table / bias fields of the other modes are searched against the source texels; the BC1 hint bits are 0.  No block can fail: there is no
+ *   status word.
+ *   Every other target follows by bu_uastc_transcode of the result, a .basis file by bu_basis_write_uastc.
+ * Device form: only enqueues two launches on `stream` (the blocks, then their ETC1 fields in place); nothing is allocated, copied or synchronised, so it may be captured into a graph.
+ * Host form: a staged call as bu_rgba_encode_blocks. */
+bu_status bu_rgba_encode_uastc_device(bu_context* ctx, const void* d_rgba, size_t width, size_t height, size_t in_pitch_bytes,
+                                      void* d_blocks, size_t out_pitch_bytes, void* stream);
+bu_status bu_rgba_encode_uastc(bu_context* ctx, const uint8_t* rgba, size_t width, size_t height, size_t in_pitch_bytes,
+                               uint8_t* out, size_t out_bytes);
+
 /* ---- whole-file level: the crate's public read_to_* API (src/lib.rs:20-22, src/basis.rs) -------------
  * Host side in C++ (container parse, CRC-16, BasisLZ entropy decode -- byte/symbol serial, stays on the CPU),
  * block work on the GPU through the entry points above. */

@@ -245,4 +245,9 @@ extern "C" {
                                                in_pitch_bytes: usize, d_blocks: *mut c_void, out_pitch_bytes: usize, stream: *mut c_void) -> c_int;
     pub(crate) fn bu_rgba_encode_blocks(ctx: *mut bu_context, format: c_int, rgba: *const u8, width: usize, height: usize, in_pitch_bytes: usize,
                                         out: *mut u8, out_bytes: usize) -> c_int;
+    // an RGBA8 image -> UASTC blocks (tests/test_gpu_uastc_encode.py; `encode_uastc` / `encode_uastc_device` of lib.rs)
+    pub(crate) fn bu_rgba_encode_uastc_device(ctx: *mut bu_context, d_rgba: *const c_void, width: usize, height: usize, in_pitch_bytes: usize,
+                                              d_blocks: *mut c_void, out_pitch_bytes: usize, stream: *mut c_void) -> c_int;
+    pub(crate) fn bu_rgba_encode_uastc(ctx: *mut bu_context, rgba: *const u8, width: usize, height: usize, in_pitch_bytes: usize, out: *mut u8,
+                                       out_bytes: usize) -> c_int;
 }

@@ -285,6 +285,35 @@ pub unsafe fn encode_blocks_device(ctx: *mut ffi::bu_context, format: c_int, d_r
     check(ctx, ffi::bu_rgba_encode_blocks_device(ctx, format, d_rgba, width, height, in_pitch_bytes, d_blocks, out_pitch_bytes, stream))
 }
 
+/// An RGBA8 image of `width` x `height` pixels in host memory, pixel rows `in_pitch_bytes` apart (0 = `4 * width`), -> UASTC blocks, `ceil(width / 4)`
+/// per block row, tight (bu_rgba_encode_uastc, no counterpart in the reference): the input of every transcode of this crate and of a .basis file.
+/// Partial edge blocks repeat the last column and row; every block is a valid single-subset UASTC block, so no block can fail.
+pub fn encode_uastc(rgba: &[u8], width: usize, height: usize, in_pitch_bytes: usize) -> Result<Vec<u8>> {
+    let ctx = context()?;
+    let pitch = if in_pitch_bytes == 0 { width.saturating_mul(4) } else { in_pitch_bytes };
+    if width > 0 && height > 0 && rgba.len() < (height - 1).saturating_mul(pitch).saturating_add(width.saturating_mul(4)) {
+        return Err("encode_uastc: rgba holds fewer bytes than the image".to_string());
+    }
+    let blocks = |pixels: usize| pixels / 4 + (pixels % 4 != 0) as usize;
+    let n = blocks(width).saturating_mul(blocks(height));
+    let mut out = vec![0u8; n.saturating_mul(16).max(1)];
+    let st = unsafe { ffi::bu_rgba_encode_uastc(ctx, rgba.as_ptr(), width, height, in_pitch_bytes, out.as_mut_ptr(), out.len()) };
+    check(ctx, st)?;
+    out.truncate(n * 16);
+    Ok(out)
+}
+
+/// The device form: the image at `d_rgba` -> UASTC blocks at `d_blocks`, block rows `out_pitch_bytes` apart (0 = tight), in one enqueue on `stream`
+/// (bu_rgba_encode_uastc_device).  Only argument and launch errors are returned.
+///
+/// # Safety
+/// `ctx` is a live context; `d_rgba` (4-byte aligned) covers `height` pixel rows of the pitch, the last up to its last pixel; `d_blocks` (16-byte
+/// aligned) covers `ceil(height / 4)` block rows of the pitch; the two do not overlap; `stream` is null or a stream of that device.
+pub unsafe fn encode_uastc_device(ctx: *mut ffi::bu_context, d_rgba: *const core::ffi::c_void, width: usize, height: usize, in_pitch_bytes: usize,
+                                  d_blocks: *mut core::ffi::c_void, out_pitch_bytes: usize, stream: *mut core::ffi::c_void) -> Result<()> {
+    check(ctx, ffi::bu_rgba_encode_uastc_device(ctx, d_rgba, width, height, in_pitch_bytes, d_blocks, out_pitch_bytes, stream))
+}
+
 /// Texture array sharded over the devices `devices` of one node (no counterpart in the reference, which walks the slices
 /// one by one: basis.rs:246-257): slice range g*n/P..(g+1)*n/P goes to device g, every device ends up holding the whole
 /// transcoded array (`gather = true`: peer pulls over xGMI), and the array is returned from device 0.
