@@ -2,7 +2,8 @@
 gap: 65 blocks (one full wave and a ragged one) in page-locked buffers that start 8 bytes past 16-byte alignment -- the kernels move 16-byte vectors, so
 such a buffer is staged like pageable memory and the bytes are the same -- beside aligned ones, which the kernels read and write directly; a clean input
 and a failing one each.  Every buffer lies between the guard bands of tests/gpu_guard.py.  Expected bytes: the golden vectors, the oracle, the decoders
-of tests/decode_cases.py, and for the encoders the identity with the transcoder (tests/test_gpu_encode_blocks.py)."""
+of tests/decode_cases.py, for the block encoders the identity with the transcoder (tests/test_gpu_encode_blocks.py), and for the UASTC encoder the numpy
+model's blocks (tests/uastc_encode_cases.py)."""
 import numpy as np
 import pytest
 
@@ -113,6 +114,23 @@ def test_encode_blocks_page_locked(ctx, golden, name, offset):
             if dst is not None:
                 dst[:] = POISON
             assert np.array_equal(ctx.encode_blocks(fmt, src, 4 * N, 4, out=dst), want), (name, offset)
+
+
+@pytest.mark.parametrize("offset", OFFSETS)
+def test_encode_uastc_page_locked(ctx, offset):
+    """the first 65 blocks of the class-mixed edge strip (tests/uastc_encode_cases.py) == the model's.  The one staged call with two kernels, the second of
+    which reads back what the first wrote into the caller's buffer and stores over it: mapped (+0) and staged (+8)"""
+    import uastc_encode_cases as uc
+
+    blocks, want, _ = uc.edge_mixed()
+    image = uc.strip(blocks[:N]).reshape(-1)
+    with Pinned(ctx, offset, image.size, N * 16) as (pin_in, pin_out):
+        assert pin_in.ctypes.data % 16 == offset and pin_out.ctypes.data % 16 == offset
+        pin_in[:] = image
+        for src, dst in ((pin_in, pin_out), (pin_in, None), (image, pin_out)):
+            if dst is not None:
+                dst[:] = POISON
+            assert np.array_equal(ctx.encode_uastc(src, 4 * N, 4, out=dst).reshape(N, 16), want[:N]), offset
 
 
 # ---- the whole-file drivers: a page-locked output, mapped and staged, of the intact file and of one whose damage both CRCs hide ---------------

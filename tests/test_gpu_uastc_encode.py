@@ -2,7 +2,8 @@
 
 The bytes are the numpy model's (tests/uastc_encode_model.py through tests/uastc_encode_cases.py, which the CPU tests judge by the oracle) on every shape
 of the case list and on the layouts where the kernel can go wrong: unaligned bases and pitches (the 4-byte load path), padded outputs, a second
-grid-stride step; with guard bands around both buffers, refusals that must leave the output alone, the host form with pageable and page-locked
+grid-stride step; on the edge families of the case list in waves of one block class and in waves that hold all four (a block's bytes must not depend
+on its lane or its wave-mates); with guard bands around both buffers, refusals that must leave the output alone, the host form with pageable and page-locked
 buffers, a graph capture, and the two compositions the encoder exists for: every transcode target of its blocks, and image -> .basis file -> read."""
 import numpy as np
 import pytest
@@ -55,6 +56,71 @@ def test_bytes_are_the_models(ctx, case):
         _same(got, want, "%s layout %s" % (uc.case_id(case), (in_pad, out_pad, off)))
 
 
+# ---- 1b. the edge families: waves of one class, waves of all four ---------------------------------------------------------------------------------
+EDGE_LAYOUTS = LAYOUTS[:2]
+
+
+def _strip_blocks(ctx, blocks, layout, seed):
+    return _encode_device(ctx, uc.strip(blocks), *layout, pad_seed=seed)[0]
+
+
+@pytest.fixture(scope="module")
+def edge_gpu(ctx):
+    """the device's blocks of edge_sorted and edge_mixed at the tight layout, encoded once"""
+    return _strip_blocks(ctx, uc.edge_sorted()[0], EDGE_LAYOUTS[0], 1), _strip_blocks(ctx, uc.edge_mixed()[0], EDGE_LAYOUTS[0], 2)
+
+
+def _family_of(i):
+    return "%s[%d]" % (list(uc.EDGE_FAMILIES)[i // 64], i % 64)
+
+
+def _same_strip(got, want, what, index=lambda i: i):
+    bad = np.nonzero((got != want).any(-1))[0]
+    assert bad.size == 0, "%s: %d blocks differ, first %d = %s: got %s, want %s" % (what, bad.size, bad[0], _family_of(int(index(bad[0]))), got[bad[0]].tobytes().hex(),
+                                                                                   want[bad[0]].tobytes().hex())
+
+
+def test_edge_blocks_are_the_models(ctx, edge_gpu):
+    blocks, want = uc.edge_sorted()
+    _same_strip(edge_gpu[0], want, "edge_sorted layout %s" % (EDGE_LAYOUTS[0],))
+    _same_strip(_strip_blocks(ctx, blocks, EDGE_LAYOUTS[1], 3), want, "edge_sorted layout %s" % (EDGE_LAYOUTS[1],))
+
+
+def test_mixed_class_waves_are_the_models(ctx, edge_gpu):
+    """every wave of the strip holds lanes of all four classes (tests/test_uastc_encode.py asserts that of the strip).  Then without the model: block i
+    of the mixed strip is block order[i] of the sorted one, encoded there in another lane beside blocks of its own family"""
+    blocks, want, order = uc.edge_mixed()
+    _same_strip(edge_gpu[1], want, "edge_mixed layout %s" % (EDGE_LAYOUTS[0],), lambda i: order[i])
+    padded = _strip_blocks(ctx, blocks, EDGE_LAYOUTS[1], 4)
+    _same_strip(padded, want, "edge_mixed layout %s" % (EDGE_LAYOUTS[1],), lambda i: order[i])
+    _same_strip(edge_gpu[1], edge_gpu[0][order], "edge_mixed against the device's own edge_sorted", lambda i: order[i])
+    _same_strip(padded, edge_gpu[0][order], "edge_mixed, padded, against the device's own edge_sorted", lambda i: order[i])
+
+
+def test_class_rule_on_the_device(edge_gpu):
+    """the class of a block's 16 texels against the mode in the device's bytes, no model between them"""
+    for what, src, got in (("edge_sorted", uc.edge_sorted()[0], edge_gpu[0]), ("edge_mixed", uc.edge_mixed()[0], edge_gpu[1])):
+        bad = uc.class_rule_violations(src, got)
+        assert bad.size == 0, "%s: blocks %s" % (what, bad[:5].tolist())
+
+
+@pytest.fixture(scope="module")
+def formula_expected():
+    import uastc_encode_model as um
+
+    return {(w, h): um.encode(ec.to_blocks(uc.formula_image(w, h))).reshape(ec.blocks_of(w, h)[::-1] + (16,)) for (w, h) in ((255, 9), (12, 203))}
+
+
+@pytest.mark.parametrize("shape", ((255, 9), (12, 203)), ids=lambda s: "%dx%d" % s)
+def test_formula_image_with_partial_blocks(ctx, formula_expected, shape):
+    """solid, opaque and RGBA classes change every 2 x 2 blocks, the last block column and row are partial"""
+    w, h = shape
+    img = uc.formula_image(w, h)
+    assert len(set(uc.block_class(ec.to_blocks(img)).tolist())) >= 3
+    for k, layout in enumerate(LAYOUTS):
+        _same(_encode_device(ctx, img, *layout, pad_seed=50 + k), formula_expected[shape], "formula image %dx%d layout %s" % (w, h, layout))
+
+
 # ---- 2. the host form ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", [("plain", "random", 255, 9), ("opaque", "gradient", 257, 8), ("grey", "gradient", 12, 203)], ids=uc.case_id)
 def test_host_form_pageable_and_page_locked(ctx, case):
@@ -76,9 +142,13 @@ def test_host_form_pageable_and_page_locked(ctx, case):
 
 
 # ---- 3. a second grid-stride step ----------------------------------------------------------------------------------------------------------------
-def test_second_grid_stride_step(ctx):
+@pytest.mark.parametrize("pattern", ("ag-gradient", "class-mixed"))
+def test_second_grid_stride_step(ctx, pattern):
     """8 * CUs * 256 + 65 blocks or a little more: the grid is capped at 8 workgroups per CU, so some lanes take a second block; the image is a
-    64 x 64-pixel pattern tiled, two pixels short of a multiple of four wide, on a 16-byte-aligned pitch (the 16-byte loads, the last column clamped)"""
+    64 x 64-pixel pattern tiled, two pixels short of a multiple of four wide, on a 16-byte-aligned pitch (the 16-byte loads, the last column clamped).
+    class-mixed: uc.mixed_pattern, whose block rows hold all four classes, and in the last 64 pixel rows -- the blocks of the second step -- the same
+    pattern rolled by one 8 x 8 tile: the stride is a whole number of pattern heights, so without the roll a lane's second block would be its first
+    again.  Asserted from the pixels: every lane that takes a second step gets a block of another class than its first, under a divergent mask"""
     import torch
 
     import uastc_encode_model as um
@@ -89,16 +159,31 @@ def test_second_grid_stride_step(ctx):
     w, h = 64 * TX - 2, 64 * TY
     nbx, nby = ec.blocks_of(w, h)
     assert nbx * nby >= 8 * cus * 256 + 65 and w % 4 != 0
-    pat = uc.image("ag", "gradient", 64, 64)
-    tile = uc.expected("ag", "gradient", 64, 64)  # [16, 16, 16]
-    edge = um.encode(ec.to_blocks(pat[:, 60:62])).reshape(16, 1, 16)  # the partial last column: pattern columns 60, 61, 61, 61
-    want = np.tile(tile, (TY, TX, 1))
-    want[:, -1:] = np.tile(edge, (TY, 1, 1))
-    d_img = torch.from_numpy(pat.copy()).cuda().repeat(TY, TX, 1).contiguous()  # [h, 64 TX, 4]: the pitch of the whole tiles, two columns unused
+    if pattern == "ag-gradient":
+        pat, tile = uc.image("ag", "gradient", 64, 64), uc.expected("ag", "gradient", 64, 64)  # [16, 16, 16]
+        last, last_tile = pat, tile
+    else:
+        pat, tile = uc.mixed_pattern(), uc.mixed_pattern_expected()
+        last, last_tile = np.roll(pat, 8, axis=1), np.roll(tile, 2, axis=1)  # (one tile = two blocks to the right)
+    # the partial last column: pattern columns 60, 61, 61, 61
+    edge, last_edge = (um.encode(ec.to_blocks(p[:, 60:62])).reshape(16, 1, 16) for p in (pat, last))
+    want = np.concatenate([np.tile(tile, (TY - 1, TX, 1)), np.tile(last_tile, (1, TX, 1))])
+    want[:-16, -1:], want[-16:, -1:] = np.tile(edge, (TY - 1, 1, 1)), last_edge
+    if pattern == "class-mixed":
+        # a lane's blocks are i and i + stride; the stride is the whole grid, 8 workgroups per CU: TY - 1 pattern heights, so the second blocks are
+        # exactly those of the last 64 pixel rows, above the same columns of the first 64
+        stride = 8 * cus * 256
+        assert stride == (TY - 1) * 16 * nbx and nbx * nby - stride == 16 * nbx
+        first_cls, second_cls = (uc.block_class(ec.to_blocks(np.tile(p, (1, TX, 1))[:, :w])) for p in (pat, last))
+        assert first_cls.size == 16 * nbx and (first_cls != second_cls).all()
+        for s in range(0, first_cls.size, 64):
+            assert len(set(first_cls[s:s + 64].tolist())) == 4 and len(set(second_cls[s:s + 64].tolist())) == 4
+    d_img = torch.cat([torch.from_numpy(pat.copy()).cuda().repeat(TY - 1, TX, 1), torch.from_numpy(last.copy()).cuda().repeat(1, TX, 1)]).contiguous()
+    assert tuple(d_img.shape) == (h, 64 * TX, 4)  # the pitch of the whole tiles, two columns unused
     d_out = torch.full((nbx * nby * 16,), POISON, dtype=torch.uint8, device="cuda")
     ctx.encode_uastc_device(d_img, w, h, d_out, in_pitch=4 * 64 * TX)
     torch.cuda.synchronize()
-    _same(d_out.cpu().numpy().reshape(nby, nbx, 16), want, "second step")
+    _same(d_out.cpu().numpy().reshape(nby, nbx, 16), want, "second step, %s" % pattern)
 
 
 # ---- 4. guard bands --------------------------------------------------------------------------------------------------------------------------------
@@ -192,17 +277,31 @@ def test_graph_capture_equals_the_direct_call(ctx):
 
 
 # ---- 7. composition: every target, and image -> file -> read ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", [("plain", "random", 255, 9), ("opaque", "gradient", 64, 64), ("grey", "random", 12, 203), ("plain", "solid", 255, 9)],
-                         ids=uc.case_id)
+ORACLE_TARGETS = {_lib.ASTC: "astc", _lib.BC7: "bc7", _lib.ETC1: "etc1", _lib.ETC2: "etc2"}
+
+
+@pytest.mark.parametrize("case", [("plain", "random", 255, 9), ("opaque", "gradient", 64, 64), ("grey", "random", 12, 203), ("plain", "solid", 255, 9), "edge-mixed"],
+                         ids=lambda c: c if isinstance(c, str) else uc.case_id(c))
 def test_every_transcode_target_takes_the_blocks(ctx, oracle, case):
     """the encoder's own output transcodes without an error (one would raise) to all eleven targets -- ten through bu_uastc_transcode, RGBA32 through
-    bu_uastc_decode_to_rgba, which is how the library spells that target -- and the RGBA32 image is the oracle's decode"""
-    _, _, w, h = case
+    bu_uastc_decode_to_rgba, which is how the library spells that target -- the four targets the oracle has are the oracle's transcode of the same
+    blocks, and the RGBA32 image is the oracle's decode"""
+    if case == "edge-mixed":
+        img = uc.strip(uc.edge_mixed()[0])
+        h, w, _ = img.shape
+    else:
+        _, _, w, h = case
+        img = uc.image(*case)
     nbx, nby = ec.blocks_of(w, h)
-    blocks = ctx.encode_uastc(uc.image(*case), w, h).copy()
+    blocks = ctx.encode_uastc(img, w, h).copy()
     for t in ALL_TARGETS:
         if t != _lib.RGBA32:
-            assert ctx.transcode(t, blocks).size == nbx * nby * _lib.BLOCK_BYTES[t]
+            got = ctx.transcode(t, blocks)
+            assert got.size == nbx * nby * _lib.BLOCK_BYTES[t]
+            if t in ORACLE_TARGETS:
+                st, bad, want = oracle.transcode(ORACLE_TARGETS[t], blocks.tobytes())
+                assert st == 0, (ORACLE_TARGETS[t], st, bad)
+                assert np.array_equal(got, want), ORACLE_TARGETS[t]
     st, bad, want = oracle.decode_to_rgba(blocks.tobytes(), nbx)
     assert st == 0, (st, bad)
     assert (ctx.decode_to_rgba(blocks, nbx) == want).all()

@@ -54,8 +54,25 @@ def emul_uastc(tmp_path_factory):
     return run
 
 
+EDGE = [("edge", name) for name in uc.EDGE_FAMILIES]  # a case of the edge set: one family of 64 blocks, 64 per row
+
+
+def _id(case):
+    return "edge-%s" % case[1] if case[0] == "edge" else uc.case_id(case)
+
+
+def _fields(case):
+    return uc.edge_fields(case[1]) if case[0] == "edge" else uc.fields(*case)
+
+
 def _src(case):
+    if case[0] == "edge":
+        return uc.edge_blocks(case[1]).astype(np.int64)
     return ec.to_blocks(uc.image(*case)).reshape(-1, 16, 4).astype(np.int64)
+
+
+def _nbx(case):
+    return 64 if case[0] == "edge" else ec.blocks_of(case[2], case[3])[0]
 
 
 def _mode_error(f, decode, src):
@@ -80,6 +97,20 @@ def test_host_build_against_the_model(emul_uastc, case):
         assert bad.size == 0, "%s pad %d: blocks (by, bx) %s differ" % (uc.case_id(case), pad, bad[:5].tolist())
 
 
+@pytest.mark.parametrize("order", ("sorted", "mixed"))
+def test_host_build_against_the_model_on_the_edge_blocks(emul_uastc, order):
+    """the edge families as a strip four pixels high, family by family and in the class-mixed order, tight and on a pitch the fast loads cannot take"""
+    blocks, want = uc.edge_sorted() if order == "sorted" else uc.edge_mixed()[:2]
+    img = uc.strip(blocks)
+    w = img.shape[1]
+    for pad in (0, 4):
+        pitch = 4 * w + pad
+        fill = np.random.default_rng(7 + pad).integers(0, 256, size=ec.image_bytes(w, 4, pitch), dtype=np.uint8)
+        got = emul_uastc(ec.pitched(img, pitch, fill), w, 4, pitch)[0]
+        bad = np.nonzero((got != want).any(-1))[0]
+        assert bad.size == 0, "%s pad %d: blocks %s differ" % (order, pad, bad[:5].tolist())
+
+
 def test_quantiser_tables_built_from_the_decode_table(emul_uastc):
     """value -> nearest level of ranges 11, 13, 19 as the product builds it from BuTables::deq == the model's, built from the ASTC specification's rows"""
     for r in (11, 13, 19):
@@ -90,10 +121,10 @@ def test_quantiser_tables_built_from_the_decode_table(emul_uastc):
 
 
 # ---- 2, 3, 4: the blocks, judged without the model ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", uc.CASES, ids=uc.case_id)
+@pytest.mark.parametrize("case", uc.CASES + EDGE, ids=_id)
 def test_oracle_accepts_every_block_and_finds_the_claimed_error(oracle, dec, case):
-    f = uc.fields(*case)
-    nbx, _ = ec.blocks_of(case[2], case[3])
+    f = _fields(case)
+    nbx = _nbx(case)
     st, bad, rgba = oracle.decode_to_rgba(f["blocks"].tobytes(), nbx)
     assert st == 0, (st, bad)
     tex, st = oracle.batch("rgba", f["blocks"])
@@ -111,12 +142,65 @@ def test_oracle_accepts_every_block_and_finds_the_claimed_error(oracle, dec, cas
         assert st == 0, (target, st, bad)
 
 
+# ---- 4b: the class rule, from the pixels and the bytes alone ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", uc.CASES + EDGE, ids=_id)
+def test_class_rule_from_the_pixels_alone(case):
+    """16 equal texels -> 8; else every A == 255 -> 5, 0 or 18; else R == G == B -> 15; else 14, 12 or 10.  near_opaque and near_grey are one texel
+    away from the next class"""
+    src = _src(case)
+    bad = uc.class_rule_violations(src, _fields(case)["blocks"])
+    assert bad.size == 0, "%s: blocks %s" % (_id(case), bad[:5].tolist())
+    if case == ("edge", "near_opaque"):
+        assert (uc.block_class(src) == 3).all() and ((src[:, :, 3] != 255).sum(1) == 1).all()
+    if case == ("edge", "near_grey"):
+        assert (uc.block_class(src) == 3).all() and ((src[:, :, 0] != src[:, :, 1]).sum(1) == 1).all() and (src[:, :, 0] == src[:, :, 2]).all()
+
+
 # ---- 5: every mode of the rule is reached -------------------------------------------------------------------------------------------------------
 def test_every_mode_is_chosen():
     seen = np.concatenate([uc.fields(*c)["mode"] for c in uc.CASES])
     assert set(seen.tolist()) == {8, 5, 0, 18, 15, 14, 12, 10}
     kept = np.concatenate([uc.fields(*c)["kept"] for c in uc.CASES])
     assert kept.any() and (~kept & (seen != 8)).any()  # the least-squares pass both wins and loses
+
+
+# the family that is there for each path of uastc_encode_model.PATHS
+PATH_FAMILY = {"csh0": "tiny", "ls_skipped": "level_tripod", "ls_tie": "tiny_opaque", "ls_neg": "two_level", "ls_sat": "two_level_opaque",
+               "eq_endpoints": "level_tripod", "anchor_swap": "anti", "mode_tie": "tiny", "alpha_flat": "one_channel_0", "hints_zero": "dark",
+               "diff": "halves"}
+
+
+def test_every_path_is_taken_and_left_alone():
+    """every path the model reports is taken by a block of the family that is there for it, and not taken by some non-solid block of the set"""
+    assert set(PATH_FAMILY) == set(um.PATHS)
+    fitted = uc.edge_field("mode") != 8
+    for path, family in PATH_FAMILY.items():
+        hits = {name: int(uc.edge_fields(name)[path].sum()) for name in uc.EDGE_FAMILIES}
+        print("%-12s %s" % (path, ", ".join("%s %d" % kv for kv in hits.items() if kv[1])))
+        assert hits[family] > 0, "no block of %s takes %s (%s)" % (family, path, um.PATHS[path])
+        assert (~uc.edge_field(path) & fitted).any(), "every non-solid block of the edge set takes %s" % path
+    assert not (uc.edge_field("ls_skipped") & uc.edge_field("kept")).any()
+
+
+def test_every_wave_of_the_mixed_strip_holds_all_four_classes():
+    """what the GPU tests rely on: class of block i of edge_mixed == i % 4, computed from the pixels; so every aligned run of 64 blocks -- one wave
+    of the kernel -- holds solid, opaque, grey-with-alpha and RGBA blocks; and the strip is a reordering that drops no block"""
+    blocks, want, order = uc.edge_mixed()
+    cls = uc.block_class(blocks)
+    assert (cls == np.arange(cls.size) % 4).all()
+    for s in range(0, cls.size, 64):
+        assert set(cls[s:s + 64].tolist()) == {0, 1, 2, 3}, "the run of 64 blocks at %d holds classes %s" % (s, sorted(set(cls[s:s + 64].tolist())))
+    sb, se = uc.edge_sorted()
+    assert set(order.tolist()) == set(range(sb.shape[0])) and (blocks == sb[order]).all() and (want == se[order]).all()
+    assert (uc.strip(blocks).reshape(4, -1, 4, 4).transpose(1, 0, 2, 3).reshape(-1, 16, 4) == blocks).all()
+    assert (ec.to_blocks(uc.strip(blocks)).reshape(-1, 16, 4) == blocks).all()  # the strip's blocks in the kernel's order are the blocks
+
+
+def test_the_mixed_pattern_mixes_the_classes_in_every_block_row():
+    cls = uc.block_class(ec.to_blocks(uc.mixed_pattern())).reshape(16, 16)
+    for row in cls:
+        assert set(row.tolist()) == {0, 1, 2, 3}
+    assert (uc.formula_image(64, 64) != uc.mixed_pattern()).any() and (uc.formula_image(64, 64)[..., [0, 3]] == uc.mixed_pattern()[..., [0, 3]]).all()
 
 
 # ---- 6: exactness -------------------------------------------------------------------------------------------------------------------------------
@@ -128,6 +212,18 @@ def test_solid_and_two_colour_blocks_are_exact(case):
         assert (f["mode"] == 8).all()
     elif case[2] * case[3] > 1:  # (a checker of one pixel is a solid block)
         assert (f["mode"] != 8).all()
+
+
+@pytest.mark.parametrize("name", ("outlier", "solid_extremes", "two_colour"))
+def test_blocks_of_at_most_two_colours_are_exact(oracle, name):
+    """arbitrary colours, not the checker's: E == 0 and the oracle's decode of the block is the source"""
+    f, src = uc.edge_fields(name), uc.edge_blocks(name).astype(np.int64)
+    word = src[:, :, 0] | src[:, :, 1] << 8 | src[:, :, 2] << 16 | src[:, :, 3] << 24
+    distinct = np.array([np.unique(w).size for w in word])
+    assert (distinct <= 2).all() and ((distinct == 1) == (f["mode"] == 8)).all()
+    assert (f["E"] == 0).all() and (f["decode"] == src).all()
+    tex, st = oracle.batch("rgba", f["blocks"])
+    assert (st == 0).all() and (tex.reshape(-1, 16, 4) == src).all()
 
 
 # ---- 7: quality gates against the parent commit's encoders ---------------------------------------------------------------------------------------
@@ -174,9 +270,9 @@ def test_uncorrelated_alpha_is_recorded_not_gated():
 
 
 # ---- 8: hints -----------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", [c for c in uc.CASES if c[0] != "opaque"], ids=uc.case_id)
+@pytest.mark.parametrize("case", [c for c in uc.CASES if c[0] != "opaque"] + [("edge", n) for n in ("one_channel_3", "bright", "dark", "near_opaque")], ids=_id)
 def test_etc2tm_and_the_alpha_the_transcoder_writes(oracle, dec, case):
-    f = uc.fields(*case)
+    f = _fields(case)
     has = np.isin(f["mode"], ALPHA_MODES)
     assert ((f["etc2tm"] >> 4) != 0)[has].all() and (f["etc2tm"][~has] == 0).all()
     etc2, st = oracle.batch("etc2", f["blocks"])
@@ -249,20 +345,30 @@ def test_etc1_hints_are_the_brute_force(oracle, dec):
             if len(picked.setdefault(m, [])) < 2:
                 picked[m].append((case, j))
     assert set(picked) == {5, 0, 18, 15, 14, 12, 10}
+    # and at the clamps: two blocks each of the families whose base colours or modifiers sit at 0 / 255 or at the differential clamp
+    for name in ("dark", "bright_opaque", "two_level_opaque", "two_level", "grey_a_anti", "ramp_sat", "halves"):
+        f = uc.edge_fields(name)
+        assert (f["mode"][[0, 33]] != 8).all()
+        for j in (0, 33):
+            picked.setdefault(int(f["mode"][j]), []).append((("edge", name), j))
+    assert sum(len(v) for v in picked.values()) == 14 + 14
     for m, blocks in picked.items():
         nb = 1 if m in (10, 12) else 32
         tuples = np.array([(fl, d, i0, i1, b) for fl in range(2) for d in range(2) for i0 in range(8) for i1 in range(8) for b in range(nb)])
         for case, j in blocks:
-            f = uc.fields(*case)
+            f = _fields(case)
             variants = _with_etc1_hints(np.repeat(f["blocks"][j:j + 1], len(tuples), 0), np.full(len(tuples), m), tuples)
             err = ((_etc1_rgb(oracle, dec, variants) - _src(case)[j, :, :3][None]) ** 2).sum((1, 2))
-            assert tuple(tuples[int(np.argmin(err))]) == tuple(f["etc1"][j]), (m, uc.case_id(case), j)
+            assert tuple(tuples[int(np.argmin(err))]) == tuple(f["etc1"][j]), (m, _id(case), j)
 
 
-@pytest.mark.parametrize("case", [c for c in uc.CASES if c[1] == "solid" or c[3] == 1], ids=uc.case_id)
+M8_EXTREMES = (0, 1, 2, 5, 6, 7, 8, 20)  # of solid_extremes, for the brute force: 0, 255, pure red, grey 7, 8, 247, 248, and a mixed colour
+
+
+@pytest.mark.parametrize("case", [c for c in uc.CASES if c[1] == "solid" or c[3] == 1] + [("edge", "solid_extremes")], ids=_id)
 def test_mode8_etc1_fields(oracle, dec, case):
     """the ETC1 block the transcoder writes for the chosen (d, i, s, r, g, b) decodes to what the model expects, and the tuple is the lowest of the best"""
-    f = uc.fields(*case)
+    f = _fields(case)
     m8 = f["mode"] == 8
     assert m8.any()
     etc1, st = oracle.batch("etc1", f["blocks"][m8])
@@ -276,7 +382,9 @@ def test_mode8_etc1_fields(oracle, dec, case):
     # optimality and the tie order, apart from um.mode8_hints: for up to four blocks, every (d, i, s) with every 5-bit value per channel (64 x 32 per
     # channel; the channels are independent for a fixed (d, i, s), so this is the brute force over all tuples), each block built and sent through the
     # oracle's transcode and the independent decoder
-    for j in np.unique(np.linspace(0, m8.sum() - 1, 4).astype(int)):
+    if case[0] == "edge":
+        assert m8.all() and [tuple(v) for v in src[[0, 1, 5, 6, 7, 8], 0]] == [(c, c, c) for c in (0, 255, 7, 8, 247, 248)]
+    for j in (M8_EXTREMES if case[0] == "edge" else np.unique(np.linspace(0, m8.sum() - 1, 4).astype(int))):
         block = f["blocks"][m8][j]
         word = int.from_bytes(block.tobytes(), "little") & ((1 << 37) - 1)
         variants, dis = [], []

@@ -83,7 +83,7 @@ def assign(x, pal):
 
 
 def fit(x, r, wb):
-    """x [n, 16, C] -> (lo index, hi index [n, C], k [n, 16], E [n], kept [n])"""
+    """x [n, 16, C] -> (lo index, hi index [n, C], k [n, 16], E [n], kept [n], paths: name -> [n] bool, the PATHS this fit took)"""
     n, _, C = x.shape
     lv, q = LEVELS[r], QUANT[r]
     S = x.sum(1)
@@ -113,21 +113,23 @@ def fit(x, r, wb):
     Sax, Sbx = (a[:, :, None] * x).sum(1), (b[:, :, None] * x).sum(1)
     det = Saa * Sbb - Sab * Sab
     assert (det >= 0).all() and (det <= (1 << 30)).all()
-    NA = np.maximum(0, Sbb[:, None] * Sax - Sab[:, None] * Sbx)
-    NB = np.maximum(0, Saa[:, None] * Sbx - Sab[:, None] * Sax)
+    rawA, rawB = Sbb[:, None] * Sax - Sab[:, None] * Sbx, Saa[:, None] * Sbx - Sab[:, None] * Sax
+    NA, NB = np.maximum(0, rawA), np.maximum(0, rawB)
     assert (NA < (1 << 36)).all() and (NB < (1 << 36)).all()
     t = np.maximum(0, _bitlen(np.maximum(NA, NB).max(-1)) - 23)
     d2 = det >> t
     ok = d2 > 0
     dd = np.where(ok, d2, 1)[:, None]
-    ra = np.minimum(255, (128 * (NA >> t[:, None]) + dd) // (2 * dd))
-    rb = np.minimum(255, (128 * (NB >> t[:, None]) + dd) // (2 * dd))
+    ua, ub = (128 * (NA >> t[:, None]) + dd) // (2 * dd), (128 * (NB >> t[:, None]) + dd) // (2 * dd)
+    ra, rb = np.minimum(255, ua), np.minimum(255, ub)
     lo2, hi2 = q[ra], q[rb]
     k2, E2 = assign(x, palette(lv[lo2], lv[hi2], wb))
     kept = ok & (E2 < E)
+    paths = dict(csh0=sh == 0, ls_skipped=~ok, ls_tie=ok & (E2 == E), ls_neg=((rawA < 0) | (rawB < 0)).any(-1),
+                 ls_sat=ok & ((ua > 255) | (ub > 255)).any(-1), eq_endpoints=(lo == hi).all(-1))
     lo, hi = np.where(kept[:, None], lo2, lo), np.where(kept[:, None], hi2, hi)
     k, E = np.where(kept[:, None], k2, k), np.where(kept, E2, E)
-    return lo, hi, k, E, kept
+    return lo, hi, k, E, kept, paths
 
 
 # ---- hints ------------------------------------------------------------------------------------------------------------------------------------
@@ -307,9 +309,26 @@ def _pack(mode, lo, hi, k, etc2tm, etc1):
     return v
 
 
+# What encode_fields reports per block beside the bytes, for the fit of the CHOSEN mode where the path is one of the fit's:
+PATHS = {
+    "csh0": "fit 1: the covariance fits 16 bits as it is, the shift is 0",
+    "ls_skipped": "fit 4: det >> t == 0, the least-squares pass is skipped",
+    "ls_tie": "fit 4: the pass ran and reached E' == E, so it is not kept",
+    "ls_neg": "fit 4: a numerator was negative and clamped at 0",
+    "ls_sat": "fit 4: a value above 255 was clamped (the pass ran)",
+    "eq_endpoints": "fit 2: L and H quantise to the same level in every channel",
+    "anchor_swap": "anchor: texel 0's index is in the upper half, the endpoints swap",
+    "mode_tie": "class: a candidate mode later in the list reached the chosen mode's E and lost",
+    "alpha_flat": "hints: a non-solid block of modes 15, 14, 12, 10 whose decoded alpha is constant (etc2tm is 0x10 without a search)",
+    "hints_zero": "hints: the ETC1 search of a non-solid block ended on (0, 0, 0, 0, 0)",
+    "diff": "hints: the chosen ETC1 fields of a non-solid block use the differential form",
+}
+
+
 def encode_fields(rgba):
     """rgba [n, 64] uint8 -> dict: mode [n], E [n] (over the mode's channels), blocks [n, 16] uint8, decode [n, 16, 4] (the UASTC decode the model
-    expects), etc2tm [n] (0 where the mode has none), m8 [n, 6], kept [n] (the least-squares pass won in the chosen mode), etc1 [n, 5]"""
+    expects), etc2tm [n] (0 where the mode has none), m8 [n, 6], kept [n] (the least-squares pass won in the chosen mode), etc1 [n, 5], and one
+    boolean [n] per name of PATHS: what the block took on its way (report only: no byte depends on them; all False in mode 8)"""
     x4 = np.asarray(rgba, dtype=np.uint8).reshape(-1, 16, 4).astype(np.int64)
     n = x4.shape[0]
     solid = (x4 == x4[:, :1]).all((1, 2))
@@ -324,6 +343,7 @@ def encode_fields(rgba):
     blocks = np.zeros((n, 16), dtype=np.uint8)
     m8 = np.zeros((n, 6), dtype=np.int64)
     etc1 = np.zeros((n, 5), dtype=np.int64)  # (flip, diff, inten0, inten1, bias) of the non-solid blocks; bias 0 where the mode has none
+    paths = {name: np.zeros(n, dtype=bool) for name in PATHS}
     words = [0] * n
     for cls, cands in ((opaque, OPAQUE), (grey, GREY), (alpha, ALPHA)):
         sel = np.nonzero(cls)[0]
@@ -333,12 +353,17 @@ def encode_fields(rgba):
         for m in cands:
             _, _, r, wb, ch = MODES[m]
             x = x4[sel][:, :, list(ch)]
-            lo, hi, k, e, kp = fit(x, r, wb)
+            lo, hi, k, e, kp, fp = fit(x, r, wb)
+            fp["anchor_swap"] = k[:, 0] >= (1 << wb) // 2
             if best is None:
-                best = dict(m=np.full(sel.size, m), lo=[None] * sel.size, hi=[None] * sel.size, k=k.copy(), e=e.copy(), kp=kp.copy())
+                best = dict(m=np.full(sel.size, m), lo=[None] * sel.size, hi=[None] * sel.size, k=k.copy(), e=e.copy(), kp=kp.copy(),
+                            tie=np.zeros(sel.size, dtype=bool), fp={name: v.copy() for name, v in fp.items()})
                 win = np.ones(sel.size, dtype=bool)
             else:
                 win = e < best["e"]
+                best["tie"] = ~win & (best["tie"] | (e == best["e"]))  # (a new winner has no later candidate yet)
+                for name, v in fp.items():
+                    best["fp"][name] = np.where(win, v, best["fp"][name])
             for j in np.nonzero(win)[0]:
                 best["lo"][j], best["hi"][j] = lo[j], hi[j]
             best["m"] = np.where(win, m, best["m"])
@@ -346,6 +371,9 @@ def encode_fields(rgba):
             best["kp"] = np.where(win, kp, best["kp"])
             best["k"] = np.where(win[:, None], k, best["k"])
         mode[sel], E[sel], kept[sel] = best["m"], best["e"], best["kp"]
+        paths["mode_tie"][sel] = best["tie"]
+        for name, v in best["fp"].items():
+            paths[name][sel] = v
         for j, g in enumerate(sel):
             m = int(best["m"][j])
             _, _, r, wb, ch = MODES[m]
@@ -360,11 +388,14 @@ def encode_fields(rgba):
                 decode[g] = d
         if cands is not OPAQUE:
             etc2tm[sel] = etc2tm_search(decode[sel][:, :, 3], x4[sel][:, :, 3])
+            paths["alpha_flat"][sel] = (decode[sel][:, :, 3] == decode[sel][:, :1, 3]).all(1)
         src3, dec3 = x4[sel][:, :, :3].reshape(-1, 4, 4, 3), decode[sel][:, :, :3].reshape(-1, 4, 4, 3)
         nb = np.isin(best["m"], (10, 12))  # (modes 10 - 12 carry no bias field)
         for grp, hb in ((nb, False), (~nb, True)):
             if grp.any():
                 etc1[sel[grp]] = etc1_search(dec3[grp], src3[grp], hb)
+        paths["hints_zero"][sel] = (etc1[sel] == 0).all(1)
+        paths["diff"][sel] = etc1[sel, 1] == 1
         for j, g in enumerate(sel):
             words[g] = _pack(int(best["m"][j]), best["lo"][j], best["hi"][j], best["k"][j], etc2tm[g], etc1[g])
     sel = np.nonzero(solid)[0]
@@ -376,7 +407,7 @@ def encode_fields(rgba):
             words[g] = 0x17 | (r | gg << 8 | b << 16 | a << 24) << 5 | d << 37 | i << 38 | s << 41 | cr << 43 | cg << 48 | cb << 53
     for g in range(n):
         blocks[g] = np.frombuffer(int(words[g]).to_bytes(16, "little"), dtype=np.uint8)
-    return dict(mode=mode, E=E, blocks=blocks, decode=decode, etc2tm=etc2tm, m8=m8, kept=kept, etc1=etc1)
+    return dict(mode=mode, E=E, blocks=blocks, decode=decode, etc2tm=etc2tm, m8=m8, kept=kept, etc1=etc1, **paths)
 
 
 def encode(rgba):
